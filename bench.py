@@ -15,9 +15,16 @@ At n_gpus > 1 the (instance, image) work units of MIS phase 1 are sharded over t
 all-gather of the unit latents each rank owns recombines them, in the fixed [instance][image] order, before the same idf_mis_merge
 call as on one GPU: north_star's split) or "image" (owner = image mod N: replicas, nothing to exchange at the merge).  Inputs are resident in HBM before the timed region.  VAE decode is outside the path.
 
-Prints ONE JSON line on rank 0 with the driver contract fields plus
+Prints ONE JSON line on rank 0 with the driver contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step,
+...).  A plain run does only the headline: set-up, ``--warmup`` untimed + ``--steps`` timed samplings, the line.
+``--full`` adds the measurements that take runs of their own:
   "roofline"     -- dominant kernel's achieved TFLOP/s (algorithmic flops / HIP-event duration) vs 2.5 PF bf16 MFMA
-  "cpu_baseline" -- the CPU oracle (port of the reference algorithm, fp32) timed on this host on a bounded sample.
+  "executed"     -- the flops the engine really ran in the timed region
+  "cpu_baseline" -- the CPU oracle (port of the reference algorithm, fp32) timed on this host on a bounded sample
+  and the short legs "reference_batch_leg" (8 images, 1 GPU), "strong_scaling_leg" (8 images in total, N > 1 GPUs) and
+  "alt_dtype_leg" (the other 16-bit type); each ``--no-*`` option below drops one of them.
+``--dump-outputs DIR`` writes the latents the last timed sampling returned as DIR/latents.npy (float32; the inputs are
+seeded, so two builds run with the same arguments can be compared output for output).
 """
 from __future__ import annotations
 
@@ -270,6 +277,22 @@ def cpu_baseline(cfg, sd, host_inputs, budget_s=25.0):
                        f"port's sampler with a call-counting forward)")
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, latents):
+    """The sampler's result of the last timed step (latents [images, 4, 64, 64]) -> out_dir/latents.npy, float32.  Beyond
+    DUMP_MAX_BYTES a fixed, seeded sample of whole images is written, in image order."""
+    import numpy as np
+    lat = latents.detach().float()
+    per_image = lat[0].numel() * 4
+    if lat.shape[0] * per_image > DUMP_MAX_BYTES:
+        keep = torch.randperm(lat.shape[0], generator=torch.Generator().manual_seed(0))[:DUMP_MAX_BYTES // per_image]
+        lat = lat[keep.sort().values.to(lat.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "latents.npy"), lat.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -286,6 +309,10 @@ def main():
     ap.add_argument("--sharding", choices=["auto", "image", "instance"], default="instance",
                     help="MIS phase-1 unit ownership at n_gpus > 1 (host/samplers.py); no effect at 1 GPU")
     ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16", help="storage / MFMA input type of the headline run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline / executed flops, the CPU baseline and the short extra legs (off: headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the latents of the last timed step as DIR/latents.npy (float32)")
     ap.add_argument("--no-alt-dtype", action="store_true", help="skip the short leg in the other 16-bit type")
     ap.add_argument("--no-strong-leg", action="store_true", help="at n_gpus > 1: skip the short strong-scaling leg (8 images total)")
     ap.add_argument("--no-ref-batch-leg", action="store_true", help="at 1 GPU: skip the short leg at the reference's own batch (8 images)")
@@ -372,10 +399,12 @@ def main():
         assert torch.isfinite(out).all()
         eng.forward_cond = real_forward
         return dict(value=n_img * steps / elapsed, ms_per_step=elapsed / max(steps, 1) * 1e3, images=n_img, steps=steps,
-                    rows_on=rows[True], rows_off=rows[False], host_inputs=host_inputs)
+                    rows_on=rows[True], rows_off=rows[False], host_inputs=host_inputs, out=out)
 
     main_leg = run_leg(args.dtype, n_images, args.steps, args.warmup, args.sharding)
     value = main_leg["value"]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, main_leg["out"])
     line = None
     if rank == 0:
         line = {
@@ -398,61 +427,63 @@ def main():
             "whole_step_algorithmic_tflops_per_gpu": round(value * nf * GFLOP_PER_FWD / 1e3 / world, 1),
             "whole_step_frac_of_mfma_peak": round(value * nf * GFLOP_PER_FWD / 1e3 / world / PEAK_MFMA_TF, 4),
         }
-    eng = model.engine
-    if rank == 0 and not args.no_roofline:
-        phase1_batch = max(eng._slots.keys())
-        line["roofline"] = measure_roofline(eng, phase1_batch, True)
-        # executed work: what the engine really ran after the exact hoists -- forward ROWS counted in the timed
-        # region (first-evaluation de-duplication included) x the GEMM / conv / attention flops of one instrumented row,
-        # with the fuser on and off (alpha == 0 steps); UniFusion and the grounding-token K/V run once per conditioning,
-        # outside the forwards, and are not counted
-        off = measure_roofline(eng, phase1_batch, False)
-        f_on = line["roofline"].pop("_flops_per_row")
-        f_off = off["_flops_per_row"]
-        ex_tf = (main_leg["rows_on"] * f_on + main_leg["rows_off"] * f_off) / 1e12          # all ranks, timed region
-        secs = main_leg["ms_per_step"] * 1e-3 * args.steps
-        line["executed"] = dict(
-            tflop_per_image=round(ex_tf / (n_images * args.steps), 1), reference_tflop_per_image=round(nf * GFLOP_PER_FWD / 1e3, 1),
-            forward_rows_per_image=round((main_leg["rows_on"] + main_leg["rows_off"]) / (n_images * args.steps), 1),
-            gflop_per_row_fuser_on=round(f_on / 1e9, 1), gflop_per_row_fuser_off=round(f_off / 1e9, 1),
-            tflops_per_gpu=round(ex_tf / secs / world, 1), frac_of_mfma_peak=round(ex_tf / secs / world / PEAK_MFMA_TF, 4))
-    if rank == 0 and not args.no_cpu_baseline and world == 1:    # reported at N=1 only (the host cores are shared at N>1)
-        line["cpu_baseline"] = cpu_baseline(cfg, sd, main_leg["host_inputs"])
-    # ---- short extra legs (outside the headline's timed region; each its own warm-up + timed samplings)
-    if world > 1 and not args.no_strong_leg and not args.images_total:
-        # strong scaling at the reference's own batch: 8 images in total (inference.py num_images), split over the ranks
-        k = 8
-        leg = run_leg(args.dtype, k, 1, 1, args.sharding)
-        if rank == 0:
-            ms = int(S_STEPS * MIS)
-            p1, p2 = (N_INST + 1) * (ms + 1), S_STEPS - ms                   # forward pairs per image: shardable / per-image serial
-            line["strong_scaling_leg"] = dict(global_images=k, value=round(leg["value"], 4), unit="img/s", steps=1, warmup=1,
-                                              ms_per_step=round(leg["ms_per_step"], 2), sharding=args.sharding,
-                                              forward_rows_per_image=round((leg["rows_on"] + leg["rows_off"]) / k, 1),
-                                              # phase 1 spreads over all ranks, phase 2 runs one trajectory per image: with fewer
-                                              # images than ranks only `k` ranks work in phase 2 (and on 2-row forwards)
-                                              amdahl_cap_vs_1gpu=round((p1 + p2) / (p1 / world + p2 / min(world, k)), 2),
-                                              ranks_idle_in_phase2=max(0, world - k))
-    if world == 1 and not args.no_ref_batch_leg and not args.images_total and args.images_per_gpu != 8:
-        # the reference's own batch: num_images = 8 per prompt (inference.py) on one GPU -- phase 1 runs
-        # 72 units as 2 x 64-row + 1 x 16-row forwards per step, phase 2 16-row forwards
-        leg = run_leg(args.dtype, 8, 1, 1, args.sharding)
-        line["reference_batch_leg"] = dict(global_images=8, value=round(leg["value"], 4), unit="img/s", steps=1, warmup=1,
-                                           ms_per_step=round(leg["ms_per_step"], 2),
-                                           forward_rows_per_image=round((leg["rows_on"] + leg["rows_off"]) / 8, 1))
-    if not args.no_alt_dtype:
-        alt = "fp16" if args.dtype == "bf16" else "bf16"
-        leg = run_leg(alt, n_images, ALT_STEPS, 1, args.sharding)
-        if rank == 0:
-            line["alt_dtype_leg"] = dict(dtype=alt, value=round(leg["value"], 4), unit="img/s", steps=ALT_STEPS, warmup=1,
-                                         ms_per_step=round(leg["ms_per_step"], 2),
-                                         note="same workload in the other 16-bit storage type (the reference's GPU path is fp16 "
-                                              "autocast, inference.py:94); fp16 parity is 10x tighter and the MFMA rate is the "
-                                              "same.  Rounds 2-4 ran this leg 5-6 % behind bf16: the d = 40 attention kept the largest "
-                                              "P of a query at 2^-1 in fp16 (2^-7 in bf16), so any score 2 log2-units above the reference "
-                                              "sent the wave through the exact re-base path; round 5 gives fp16 the same 2^-7 headroom "
-                                              "(attention4.hip RefShift; small P become fp16 denormals, which the conversion produces and "
-                                              "the MFMA consumes exactly)")
+    # ---- --full: measurements with runs of their own (outside the headline's timed region)
+    if args.full:
+        eng = model.engine
+        if rank == 0 and not args.no_roofline:
+            phase1_batch = max(eng._slots.keys())
+            line["roofline"] = measure_roofline(eng, phase1_batch, True)
+            # executed work: what the engine really ran after the exact hoists -- forward ROWS counted in the timed
+            # region (first-evaluation de-duplication included) x the GEMM / conv / attention flops of one instrumented row,
+            # with the fuser on and off (alpha == 0 steps); UniFusion and the grounding-token K/V run once per conditioning,
+            # outside the forwards, and are not counted
+            off = measure_roofline(eng, phase1_batch, False)
+            f_on = line["roofline"].pop("_flops_per_row")
+            f_off = off["_flops_per_row"]
+            ex_tf = (main_leg["rows_on"] * f_on + main_leg["rows_off"] * f_off) / 1e12          # all ranks, timed region
+            secs = main_leg["ms_per_step"] * 1e-3 * args.steps
+            line["executed"] = dict(
+                tflop_per_image=round(ex_tf / (n_images * args.steps), 1), reference_tflop_per_image=round(nf * GFLOP_PER_FWD / 1e3, 1),
+                forward_rows_per_image=round((main_leg["rows_on"] + main_leg["rows_off"]) / (n_images * args.steps), 1),
+                gflop_per_row_fuser_on=round(f_on / 1e9, 1), gflop_per_row_fuser_off=round(f_off / 1e9, 1),
+                tflops_per_gpu=round(ex_tf / secs / world, 1), frac_of_mfma_peak=round(ex_tf / secs / world / PEAK_MFMA_TF, 4))
+        if rank == 0 and not args.no_cpu_baseline and world == 1:    # reported at N=1 only (the host cores are shared at N>1)
+            line["cpu_baseline"] = cpu_baseline(cfg, sd, main_leg["host_inputs"])
+        # ---- short extra legs (outside the headline's timed region; each its own warm-up + timed samplings)
+        if world > 1 and not args.no_strong_leg and not args.images_total:
+            # strong scaling at the reference's own batch: 8 images in total (inference.py num_images), split over the ranks
+            k = 8
+            leg = run_leg(args.dtype, k, 1, 1, args.sharding)
+            if rank == 0:
+                ms = int(S_STEPS * MIS)
+                p1, p2 = (N_INST + 1) * (ms + 1), S_STEPS - ms                   # forward pairs per image: shardable / per-image serial
+                line["strong_scaling_leg"] = dict(global_images=k, value=round(leg["value"], 4), unit="img/s", steps=1, warmup=1,
+                                                  ms_per_step=round(leg["ms_per_step"], 2), sharding=args.sharding,
+                                                  forward_rows_per_image=round((leg["rows_on"] + leg["rows_off"]) / k, 1),
+                                                  # phase 1 spreads over all ranks, phase 2 runs one trajectory per image: with fewer
+                                                  # images than ranks only `k` ranks work in phase 2 (and on 2-row forwards)
+                                                  amdahl_cap_vs_1gpu=round((p1 + p2) / (p1 / world + p2 / min(world, k)), 2),
+                                                  ranks_idle_in_phase2=max(0, world - k))
+        if world == 1 and not args.no_ref_batch_leg and not args.images_total and args.images_per_gpu != 8:
+            # the reference's own batch: num_images = 8 per prompt (inference.py) on one GPU -- phase 1 runs
+            # 72 units as 2 x 64-row + 1 x 16-row forwards per step, phase 2 16-row forwards
+            leg = run_leg(args.dtype, 8, 1, 1, args.sharding)
+            line["reference_batch_leg"] = dict(global_images=8, value=round(leg["value"], 4), unit="img/s", steps=1, warmup=1,
+                                               ms_per_step=round(leg["ms_per_step"], 2),
+                                               forward_rows_per_image=round((leg["rows_on"] + leg["rows_off"]) / 8, 1))
+        if not args.no_alt_dtype:
+            alt = "fp16" if args.dtype == "bf16" else "bf16"
+            leg = run_leg(alt, n_images, ALT_STEPS, 1, args.sharding)
+            if rank == 0:
+                line["alt_dtype_leg"] = dict(dtype=alt, value=round(leg["value"], 4), unit="img/s", steps=ALT_STEPS, warmup=1,
+                                             ms_per_step=round(leg["ms_per_step"], 2),
+                                             note="same workload in the other 16-bit storage type (the reference's GPU path is fp16 "
+                                                  "autocast, inference.py:94); fp16 parity is 10x tighter and the MFMA rate is the "
+                                                  "same.  Rounds 2-4 ran this leg 5-6 % behind bf16: the d = 40 attention kept the largest "
+                                                  "P of a query at 2^-1 in fp16 (2^-7 in bf16), so any score 2 log2-units above the reference "
+                                                  "sent the wave through the exact re-base path; round 5 gives fp16 the same 2^-7 headroom "
+                                                  "(attention4.hip RefShift; small P become fp16 denormals, which the conversion produces and "
+                                                  "the MFMA consumes exactly)")
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:

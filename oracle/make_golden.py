@@ -718,6 +718,20 @@ def gen_full_c2(tag="full_box_c2_s50", S=50, alpha_type=(0.8, 0.0, 0.2)):
     torch.save(out, os.path.join(GOLD, f"{tag}.pt"))
 
 
+def gen_ref_configs(names=("test_box.yaml", "test_mask.yaml", "test_point.yaml", "test_scribble.yaml"),
+                    sections=("model", "diffusion", "grounding_tokenizer_input")):
+    """The reference's configs/*.yaml as PyYAML parses them (shim 3), the sections the sampling path instantiates:
+    tests/test_capi.py resolves them to this implementation without the reference tree."""
+    out = {}
+    for name in names:
+        with open(os.path.join(REF, "configs", name)) as f:
+            cfg = yaml.safe_load(f)
+        out[name] = {k: cfg[k] for k in sections}
+    with open(os.path.join(GOLD, "ref_configs.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="all")
@@ -776,6 +790,8 @@ def main():
         gen_clip_case()
     if args.only in ("all", "plms_mask"):
         gen_plms_mask_case()
+    if args.only in ("all", "configs"):
+        gen_ref_configs()
     print("done")
 
 

@@ -36,3 +36,21 @@ def test_make_inputs_equals_materialised_construction():
         assert all(torch.equal(v, r[k]) for k, v in inputs[i + 1]["grounding_input"].items())
         assert inputs[i + 1]["grounding_input"]["segs"].stride(0) == 0          # 31 MB/sample stays ONE plane set
     assert host["gb"]["boxes"].shape[0] == 1
+
+
+def test_dump_outputs_writes_float32_and_bounds_size(tmp_path):
+    import numpy as np
+    lat = torch.randn(3, 4, bench.LATENT, bench.LATENT, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "small"), lat)
+    a = np.load(tmp_path / "small" / "latents.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, lat.float().numpy())
+    # beyond 64 MB: the same seeded sample of whole images, in image order, every time
+    n = 1100
+    big = torch.arange(n, dtype=torch.float32).view(n, 1, 1, 1).expand(n, 4, bench.LATENT, bench.LATENT)
+    for d in ("big1", "big2"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    b1, b2 = np.load(tmp_path / "big1" / "latents.npy"), np.load(tmp_path / "big2" / "latents.npy")
+    assert b1.nbytes <= bench.DUMP_MAX_BYTES and b1.shape[0] == bench.DUMP_MAX_BYTES // b1[0].nbytes
+    assert np.array_equal(b1, b2)
+    ids = b1[:, 0, 0, 0]
+    assert (np.diff(ids) > 0).all() and (b1 == ids[:, None, None, None]).all()

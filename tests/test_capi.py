@@ -247,20 +247,20 @@ def test_schema_matches_reference():
 
 @pytest.mark.parametrize("name", ["test_box.yaml", "test_mask.yaml", "test_point.yaml", "test_scribble.yaml"])
 def test_reference_yaml_instantiates(name):
-    """The reference's own YAMLs (when the reference tree is present) resolve to this implementation unchanged."""
+    """The reference's own YAMLs (as parsed, golden ``ref_configs.json``, oracle/make_golden.py:gen_ref_configs) and this
+    repo's configs/ copy of them resolve to this implementation unchanged."""
+    import json
     import torch
-    path = os.path.join("/root/reference/configs", name)
-    if not os.path.exists(path):
-        path = os.path.join(REPO, "configs", name)
     from instancediffusion_amd.host.config import instantiate_from_config, load_yaml
-    cfg = load_yaml(path)
-    with torch.device("meta"):
-        model = instantiate_from_config(cfg["model"])
-    diffusion = instantiate_from_config(cfg["diffusion"])
-    gi = instantiate_from_config(cfg["grounding_tokenizer_input"])
-    assert type(model).__module__.startswith("instancediffusion_amd")
-    assert diffusion.num_timesteps == 1000 and abs(float(diffusion.betas[0]) - 0.00085) < 1e-9
-    assert model.position_net.eval_drops() is not None and hasattr(gi, "get_null_input")
+    ref = json.load(open(os.path.join(REPO, "tests", "golden", "ref_configs.json")))[name]
+    for cfg in (ref, load_yaml(os.path.join(REPO, "configs", name))):
+        with torch.device("meta"):
+            model = instantiate_from_config(cfg["model"])
+        diffusion = instantiate_from_config(cfg["diffusion"])
+        gi = instantiate_from_config(cfg["grounding_tokenizer_input"])
+        assert type(model).__module__.startswith("instancediffusion_amd")
+        assert diffusion.num_timesteps == 1000 and abs(float(diffusion.betas[0]) - 0.00085) < 1e-9
+        assert model.position_net.eval_drops() is not None and hasattr(gi, "get_null_input")
 
 
 def test_inference_cli_input_builder():

@@ -6,8 +6,8 @@ export TMPDIR=/tmp
 R=$PWD
 O=$R/gpurun_out/r02_final
 mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err
-( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_bench -- python $R/bench.py --no-cpu-baseline --no-alt-dtype > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err )
+python bench.py --full > $O/bench.json 2> $O/bench.err
+( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_bench -- python $R/bench.py --full --no-cpu-baseline --no-alt-dtype > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err )
 ( cd /tmp && rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python $R/tools/profile_forward.py 64 2 > $O/pmc_fetch.log 2>&1 )
 ( cd /tmp && rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python $R/tools/profile_forward.py 64 2 > $O/pmc_write.log 2>&1 )
 ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_fwd -- python $R/tools/profile_forward.py 64 3 > $O/fwd_stats.log 2>&1 )
