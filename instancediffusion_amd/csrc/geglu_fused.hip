@@ -18,19 +18,17 @@
 // in, M % 128 == 0 and M >= two tiles per CU; everything else stays on gemm_big.hip.  Same arithmetic per output element as the
 // persistent kernel up to the order of the K sum (two partial sums) and the fma contraction of the fold.
 // LDS: 2 x 40 KB ring + 40 KB (c | d of all 5120 packed rows) + 4 x 4 KB staging = 136 KB.
-#include "gemm_core.h"
-#include "mw_prims.h"
-#include <cstdlib>
-#include <atomic>
+#include "mw_row.h"
 
 using namespace idfcore;
 using namespace idfmw;
 
 namespace {
 
-constexpr int GW_BM = 128, GW_K = 640, GW_N = 5120, GW_NCH = GW_N / 32;          // 160 chunks of 32 packed rows
-constexpr int GW_SLOT = 10 * 32 * 128;                                            // one W chunk: 10 K-tiles x [32 rows][64 k]
-constexpr int GW_CD_OFF = 2 * GW_SLOT, GW_STG_OFF = GW_CD_OFF + 2 * GW_N * 4, GW_SMEM = GW_STG_OFF + 4 * 4096;
+constexpr int GW_N = 5120;                                                        // 160 chunks of 32 packed rows
+using GwRow = Row640<GW_N>;
+constexpr int GW_STG_OFF = GwRow::TAIL_OFF, GW_SMEM = GW_STG_OFF + 4 * 4096;
+static_assert(GW_SMEM == 136 * 1024, "LDS budget in the header comment");
 
 struct GwParams {
   const unsigned short* x; int ldx;
@@ -60,89 +58,35 @@ template <int DT>
 __global__ __launch_bounds__(256, 1) void geglu640w_kernel(const GwParams p, const int tiles) {
   asm volatile("" ::: "a0", "a161");               // the asm-owned AGPR block: x fragments a0..a159, a160:161 the next tile's (mu, rstd)
   extern __shared__ __attribute__((aligned(128))) char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, hi = lane >> 5;
-  const int G = gridDim.x;
-  const unsigned smem_lds = lds_u32(smem);
-
   GwCtx c;
   c.k1 = 1.0142652e-3f; c.k2 = -1.0677574e-1f; c.k3 = -2.3011213f; c.one = 1.0f; c.lo8 = -8.0f; c.hi8 = 8.0f;
   asm volatile("" : "+v"(c.k1), "+v"(c.k2), "+v"(c.k3), "+v"(c.one), "+v"(c.hi8));
-  // LDS-DMA roles: piece kt of wave w = rows 8 w .. + 7 of K-tile kt of the chunk: lane -> row + lane / 8, 16-B slot lane % 8
-  unsigned w1_voff;
-  {
-    const int row = 8 * wave + (lane >> 3);
-    w1_voff = (unsigned)(row * p.ldw + (((lane & 7) ^ ((row >> 1) & 7)) << 3)) * 2u;
-  }
-  c.wb = reinterpret_cast<const char*>(p.w);
-  const unsigned w_chunk = (unsigned)(32 * p.ldw * 2);
-  const int sw1 = (l31 >> 1) & 7;
-  unsigned w1o[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) w1o[i] = smem_lds + (unsigned)(l31 * 128 + (((2 * i + hi) ^ sw1) << 4));
-  // staging image of the wave: [32 rows][128 B = the 64 output columns of four chunks], 16-B slot ^= (row >> 1) & 7; a lane
-  // writes 8 B of slots 2 jj + q (+ 8 hi inside the slot) of its row, reads back rows lane / 8 + 8 i, slot lane % 8
-  const unsigned stg = smem_lds + (unsigned)(GW_STG_OFF + wave * 4096);
-  const unsigned qwb = stg + (unsigned)(l31 * 128 + 8 * hi + (sw1 << 4));
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = (lane >> 3) + 8 * i;
-    c.qr[i] = stg + (unsigned)(row * 128 + (((lane & 7) ^ ((row >> 1) & 7)) << 4));
-    c.qst[i] = (unsigned)(row * p.ldo * 2 + (lane & 7) * 16);
-  }
-  const unsigned cd_lds = smem_lds + (unsigned)GW_CD_OFF;
+  GwRow k;
+  k.init(smem, p.x, p.ldx, p.ln_stats, p.w, p.ldw, c);
+  const int wave = k.r.wave, hi = k.r.hi, G = k.G;
+  // staging image of the wave (mw_row.h): [32 rows][128 B = the 64 output columns of four chunks]; a lane writes slots 2 jj + q
+  const unsigned qwb = mw_stage_image(k.r, k.smem_lds + (unsigned)(GW_STG_OFF + wave * 4096), p.ldo, c.qr, c.qst);
 
-  int tile = ((G & 7) == 0) ? (int)(blockIdx.x & 7) * (G >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+  int tile = mw_first_tile(G);
   if (tile >= tiles) return;
-
-  // kernel prologue: c | d of all 5120 packed rows into LDS, W chunk 0 into ring slot 0, the first tile's rows and statistics
-  for (int i = tid; i < GW_N / 4; i += 256) {
-    reinterpret_cast<f32x4*>(smem + GW_CD_OFF)[i] = reinterpret_cast<const f32x4*>(p.c)[i];
-    reinterpret_cast<f32x4*>(smem + GW_CD_OFF + GW_N * 4)[i] = reinterpret_cast<const f32x4*>(p.d)[i];
-  }
-#pragma unroll
-  for (int kt = 0; kt < 10; ++kt) mw_dma_rt(c.wb + kt * 128, w1_voff, smem_lds + (unsigned)(wave * 1024 + kt * 4096));
-  auto row_ptr = [&](int t) { return p.x + (size_t)(t * GW_BM + wave * 32 + l31) * p.ldx + 8 * hi; };
-  auto st_ptr = [&](int t) { return p.ln_stats + 2 * (size_t)(t * GW_BM + wave * 32 + l31); };
-  {
-    const unsigned short* xr = row_ptr(tile);
-    mw_static_for<40>([&](auto kc) { mw_load_x2<decltype(kc)::value, decltype(kc)::value>(xr); });
-    const float* sp = st_ptr(tile);
-    asm volatile("global_load_dwordx2 a[160:161], %0, off" ::"v"(sp) : "memory");
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
+  k.prologue(smem, p.c, p.d, tile, c);
 
   f32x16 acc[2][2];
-  // step i of a tile: epilogue of chunk i; MFMAs of chunk i + 1 [ring slot (i + 1) & 1: 160 chunks per tile, the parity carries
-  // over]; its LDS-DMA pieces bring chunk i + 2 [slot i & 1]
   auto set_step = [&](int i) {
-    const unsigned sn = (unsigned)(((i + 1) & 1) * GW_SLOT), sj = (unsigned)((i & 1) * GW_SLOT);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) c.w1a[k] = w1o[k] + sn;
-    int j2 = i + 2;
-    if (j2 >= GW_NCH) j2 -= GW_NCH;
-    c.w1_vj = w1_voff + (unsigned)j2 * w_chunk;
-    c.w1dst = smem_lds + sj + (unsigned)(wave * 1024);
-    c.cda = cd_lds + (unsigned)((32 * i + 4 * hi) * 4);
+    k.set_ring(i, c);
+    c.cda = k.cd_lds + (unsigned)((32 * i + 4 * hi) * 4);
     const int jj = i & 3;
 #pragma unroll
     for (int q = 0; q < 2; ++q) c.qwj[q] = qwb ^ (unsigned)(16 * (2 * jj + q));
-    c.obase = reinterpret_cast<const char*>(p.out) + ((size_t)tile * GW_BM + wave * 32) * p.ldo * 2 + (size_t)(i >> 2) * 128;
+    c.obase = reinterpret_cast<const char*>(p.out) + ((size_t)tile * R640_BM + wave * 32) * p.ldo * 2 + (size_t)(i >> 2) * 128;
   };
 
   for (;;) {
-    {
-      const float mu = __uint_as_float(mw_agpr_read<160>()), rs = __uint_as_float(mw_agpr_read<161>());
-      c.nmu = -mu; c.rstd = rs;
-      asm volatile("" : "+v"(c.nmu), "+v"(c.rstd));
-    }
+    k.tile_stats(c);
     const int next = tile + G;
     c.has_next = next < tiles;
-    c.xnext = row_ptr(c.has_next ? next : tile);
-    c.snext = st_ptr(c.has_next ? next : tile);
+    c.xnext = k.row_ptr(c.has_next ? next : tile);
+    c.snext = k.st_ptr(c.has_next ? next : tile);
 
     set_step(-1);
     gw_pro<DT, 0>(acc[1], acc[0], c);                              // MFMAs of chunk 0 -> acc[0]; the pieces of chunk 1
@@ -155,7 +99,7 @@ __global__ __launch_bounds__(256, 1) void geglu640w_kernel(const GwParams p, con
     gw_step<DT, 0>(acc[0], acc[1], c);
     set_step(3);
     gw_step_st<DT, 0>(acc[1], acc[0], c);
-    for (int i = 4; i < GW_NCH - 4; i += 4) {                      // steps 4 .. 155
+    for (int i = 4; i < GwRow::NCH - 4; i += 4) {                      // steps 4 .. 155
       set_step(i);
       gw_step<DT, 4>(acc[0], acc[1], c);                           // (behind the four stores of step i - 1)
       set_step(i + 1);
@@ -165,13 +109,13 @@ __global__ __launch_bounds__(256, 1) void geglu640w_kernel(const GwParams p, con
       set_step(i + 3);
       gw_step_st<DT, 0>(acc[1], acc[0], c);
     }
-    set_step(GW_NCH - 4);
+    set_step(GwRow::NCH - 4);
     gw_step<DT, 4>(acc[0], acc[1], c);
-    set_step(GW_NCH - 3);
+    set_step(GwRow::NCH - 3);
     gw_step<DT, 0>(acc[1], acc[0], c);
-    set_step(GW_NCH - 2);
+    set_step(GwRow::NCH - 2);
     gw_step<DT, 0>(acc[0], acc[1], c);
-    set_step(GW_NCH - 1);
+    set_step(GwRow::NCH - 1);
     gw_last<DT, 0>(acc[1], acc[0], c);                             // epilogue of chunk 159 + the store group; the next tile's rows first
     if (!c.has_next) break;
     tile = next;
@@ -179,44 +123,20 @@ __global__ __launch_bounds__(256, 1) void geglu640w_kernel(const GwParams p, con
   }
 }
 
-template <int DT>
-int launch_geglu640w(const GwParams& p, hipStream_t s) {
-  void (*kern)(const GwParams, const int) = geglu640w_kernel<DT>;
-  static std::atomic<unsigned long long> attr_done{0};
-  if (const int e = idf_lds_optin(reinterpret_cast<const void*>(kern), GW_SMEM, attr_done)) return e;
-  const int cus = idf_num_cu();
-  const int tiles = p.M / GW_BM;
-  const int grid = tiles < cus ? tiles : cus;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), GW_SMEM, s, p, tiles);
-  return idf_launch_status();
-}
-
-int g_gegluw_mode = -1;
-inline int gegluw_mode() {
-  if (g_gegluw_mode < 0) { const char* e = getenv("IDF_GEGLU_ROW"); g_gegluw_mode = e ? (e[0] == '0' ? 0 : 1) : 1; }
-  return g_gegluw_mode;
-}
+MwKnob g_gegluw_knob{"IDF_GEGLU_ROW", 1};
 
 }  // namespace
 
-int idf_gegluw_set_mode(int v) {
-  const int prev = gegluw_mode();
-  g_gegluw_mode = v;
-  return prev;
-}
+int idf_gegluw_set_mode(int v) { return g_gegluw_knob.set(v); }
 
 // idf_gemm tries this first for GEGLU launches; IDF_BIG_UNSUPPORTED = the shape / epilogue is not this kernel's
 int idf_launch_geglu640w(const idfcore::CoreParams& p, int dtype, hipStream_t s) {
-  if (gegluw_mode() == 0) return IDF_BIG_UNSUPPORTED;
-  if (p.K != GW_K || p.N != GW_N || !p.out || p.vt_out) return IDF_BIG_UNSUPPORTED;
-  if ((p.M % GW_BM) || p.M < GW_BM * 2 * idf_num_cu()) return IDF_BIG_UNSUPPORTED;
-  if (p.epi != (IDF_EPI_BIAS | IDF_EPI_GEGLU | IDF_EPI_GEGLU_P32 | IDF_EPI_LN_ROW) || !p.ln_stats || p.stride_ln_stats || !p.ln_c || !p.bias) return IDF_BIG_UNSUPPORTED;
-  if (dtype != IDF_BF16 && dtype != IDF_F16) return IDF_BIG_UNSUPPORTED;
-  if (p.lda < GW_K || p.ldw < GW_K || p.ldo < GW_N / 2 || (p.lda % 8) || (p.ldw % 8) || (p.ldo % 8)) return IDF_BIG_UNSUPPORTED;
-  if (!aligned16(p.A) || !aligned16(p.W) || !aligned16(p.out) || !aligned16(p.ln_c) || !aligned16(p.bias) || p.stat_parts || p.ln_stats_out) return IDF_BIG_UNSUPPORTED;
-  if ((long long)GW_N * p.ldw * 2 >= (1ll << 31) || (long long)GW_BM * p.ldo * 2 >= (1ll << 31)) return IDF_BIG_UNSUPPORTED;
+  if (g_gegluw_knob.get() == 0) return IDF_BIG_UNSUPPORTED;
+  if (!mw_row_eligible(p, dtype, R640_K, GW_N, R640_BM, GW_N / 2) || p.vt_out) return IDF_BIG_UNSUPPORTED;
+  if (p.epi != (IDF_EPI_BIAS | IDF_EPI_GEGLU | IDF_EPI_GEGLU_P32 | IDF_EPI_LN_ROW) || p.stat_parts || p.ln_stats_out) return IDF_BIG_UNSUPPORTED;
   GwParams q;
   q.x = p.A; q.ldx = p.lda; q.ln_stats = p.ln_stats; q.w = p.W; q.ldw = p.ldw; q.c = p.ln_c; q.d = p.bias;
   q.out = static_cast<unsigned short*>(p.out); q.ldo = p.ldo; q.M = p.M;
-  return dtype == IDF_BF16 ? launch_geglu640w<IDF_BF16>(q, s) : launch_geglu640w<IDF_F16>(q, s);
+  return dtype == IDF_BF16 ? mw_row_launch<GwParams, geglu640w_kernel<IDF_BF16>, GW_SMEM, R640_BM>(q, s)
+                           : mw_row_launch<GwParams, geglu640w_kernel<IDF_F16>, GW_SMEM, R640_BM>(q, s);
 }

@@ -26,10 +26,7 @@
 // Numerics: as the two-GEMM path -- fp32 accumulation, H rounded to the 16-bit type before the second product -- up to the
 // summation order of the second GEMM.  LDS: 2 x 61 KB ring + 8 KB exchange + 16 KB epilogue staging = 146 KB.
 // Roofline: MFMA-bound, 2 * M * (2560 * 320 + 320 * 1280) flops; HBM: 2 B in + 2 B out per element of x (+ residual read).
-#include "gemm_core.h"
-#include "mw_prims.h"
-#include <cstdlib>
-#include <atomic>
+#include "mw_row.h"
 #include <type_traits>
 #include <utility>
 
@@ -104,20 +101,15 @@ template <int DT>
 __global__ __launch_bounds__(512, 2) void mlp320_kernel(const MlpParams p, const int tiles) {
   constexpr bool PF = true, SK = true;
   extern __shared__ __attribute__((aligned(128))) char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, hi = lane >> 5;
+  const RowLane rl = mw_row_lane();
+  const int tid = rl.tid, lane = rl.lane, wave = rl.wave, l31 = rl.l31, hi = rl.hi;
   const int wn = wave & 1, wm = wave >> 1;
   const int G = gridDim.x;
 
   // ---- LDS-DMA roles (per-lane source offsets are the same for every chunk; the chunk moves the wave-uniform base)
   // W1: piece (t, wave) = rows 8 wave .. + 7 of K-tile t: lane -> row 8 wave + lane / 8, slot lane % 8
-  unsigned w1_voff, w2_voff[3];
-  {
-    const int row = 8 * wave + (lane >> 3);
-    const int src = (lane & 7) ^ ((row >> 1) & 7);
-    w1_voff = (unsigned)(row * p.ldw1 + src * 8) * 2u;
-  }
+  const unsigned w1_voff = mw_w1_voff(rl, p.ldw1);
+  unsigned w2_voff[3];
   // W2: piece i = rows 16 i .. + 15: lane -> row 16 i + lane / 4, slot lane % 4; pieces wave, wave + 8, (wave + 16 < 20)
 #pragma unroll
   for (int t = 0; t < 3; ++t) {
@@ -163,7 +155,7 @@ __global__ __launch_bounds__(512, 2) void mlp320_kernel(const MlpParams p, const
   char* const xch_peer = smem + XCH_OFF + (wave ^ 1) * 1024 + lane * 16;
   char* const stg = smem + STG_OFF + wave * 2048;
 
-  int tile = ((G & 7) == 0) ? (int)(blockIdx.x & 7) * (G >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+  int tile = mw_first_tile(G);
   if (tile >= tiles) return;
   const float gate = p.gate ? p.gate[0] : 1.0f;
 
@@ -335,19 +327,6 @@ __global__ __launch_bounds__(512, 2) void mlp320_kernel(const MlpParams p, const
   MTR_DUMP
 }
 
-template <int DT>
-int launch_mlp320(const MlpParams& p, hipStream_t s) {
-  void (*kern)(const MlpParams, const int) = mlp320_kernel<DT>;
-  static std::atomic<unsigned long long> attr_done{0};
-  if (const int e = idf_lds_optin(reinterpret_cast<const void*>(kern), MLP_SMEM, attr_done)) return e;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  const int tiles = p.M / MLP_BM;
-  const int grid = tiles < cus ? tiles : cus;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), MLP_SMEM, s, p, tiles);
-  return idf_launch_status();
-}
-
 
 // ====================================================================================================================
 // mlp320w_kernel -- the same feed-forward as ONE INSTRUCTION STREAM PER SIMD (round 6).
@@ -394,7 +373,7 @@ struct MwCtx {
 #endif
 };
 
-// Optional cycle trace (tools/build_mlpw_variant.sh <name> MW_TRACE=1 -- -DIDF_MLPW_TRACE; read through idf_mlpw_trace_read by
+// Optional cycle trace (tools/build_row_variant.sh mlpw <name> MW_TRACE=1 -- -DIDF_MLPW_TRACE; read through idf_mlpw_trace_read by
 // tools/ubench/mlp_harness.hip; the shipped library has none of it).  The marks are s_memtime into separate SGPR pairs, read
 // only at the end of the body: a wait for one of them inside the stream would also wait for the stream's LDS reads.
 #ifdef IDF_MLPW_TRACE
@@ -419,9 +398,8 @@ template <int DT>
 __global__ __launch_bounds__(256, 1) void mlp320w_kernel(const MlpParams p, const int tiles) {
   asm volatile("" ::: "a0", "a239");               // the asm-owned AGPR block: this is where the kernel descriptor learns its size
   extern __shared__ __attribute__((aligned(128))) char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, hi = lane >> 5;
+  const RowLane rl = mw_row_lane();
+  const int tid = rl.tid, lane = rl.lane, wave = rl.wave, l31 = rl.l31, hi = rl.hi;
   const int G = gridDim.x;
   const unsigned smem_lds = lds_u32(smem);
 
@@ -434,8 +412,7 @@ __global__ __launch_bounds__(256, 1) void mlp320w_kernel(const MlpParams p, cons
   // LDS-DMA roles.  W1: piece (kt, u) = rows 8 (wave + 4 u) .. + 7 of K-tile kt (lane -> row + lane / 8, 16-B slot lane % 8; the
   // swizzle (row >> 1) & 7 does not depend on u); W2: piece t = rows 16 (wave + 4 t) .. + 15 (lane -> row + lane / 4, slot lane % 4)
   {
-    const int row = 8 * wave + (lane >> 3);
-    c.w1_voff = (unsigned)(row * p.ldw1 + (((lane & 7) ^ ((row >> 1) & 7)) << 3)) * 2u;
+    c.w1_voff = mw_w1_voff(rl, p.ldw1);
     const int row2 = 16 * wave + (lane >> 2);
     c.w2_voff = (unsigned)(row2 * p.ldw2 + (((lane & 3) ^ ((row2 >> 2) & 3)) << 3)) * 2u;
     c.cd_voff = (unsigned)((lane & 31) * 16);
@@ -444,10 +421,9 @@ __global__ __launch_bounds__(256, 1) void mlp320w_kernel(const MlpParams p, cons
   }
   // fragment addressing (the 8-wave kernel's LDS image): W1 row 32 f + l31 of a K-tile, 16-B slot (2 (ks & 3) + hi) ^ sw1;
   // W2 row 32 a + l31, slot (2 kk + hi) ^ sw2
-  const int sw1 = (l31 >> 1) & 7, sw2 = (l31 >> 2) & 3;
+  const int sw2 = (l31 >> 2) & 3;
   unsigned w1o[4], w2o[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) w1o[i] = smem_lds + (unsigned)(l31 * 128 + (((2 * i + hi) ^ sw1) << 4));
+  mw_w1_frag(rl, smem_lds, w1o);
 #pragma unroll
   for (int kk = 0; kk < 2; ++kk) w2o[kk] = smem_lds + (unsigned)(W1_BYTES + l31 * 64 + (((2 * kk + hi) ^ sw2) << 4));
   const unsigned cdo = smem_lds + (unsigned)(W1_BYTES + W2_BYTES + 16 * hi);
@@ -480,7 +456,7 @@ __global__ __launch_bounds__(256, 1) void mlp320w_kernel(const MlpParams p, cons
     c.cddst = smem_lds + sn + (unsigned)(W1_BYTES + W2_BYTES);
   };
 
-  int tile = ((G & 7) == 0) ? (int)(blockIdx.x & 7) * (G >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+  int tile = mw_first_tile(G);
   if (tile >= tiles) return;
   const float gate = p.gate ? p.gate[0] : 1.0f;
 
@@ -643,37 +619,16 @@ __global__ __launch_bounds__(256, 1) void mlp320w_kernel(const MlpParams p, cons
 #endif
 }
 
-template <int DT>
-int launch_mlp320w(const MlpParams& p, hipStream_t s) {
-  void (*kern)(const MlpParams, const int) = mlp320w_kernel<DT>;
-  static std::atomic<unsigned long long> attr_done{0};
-  if (const int e = idf_lds_optin(reinterpret_cast<const void*>(kern), MW_SMEM, attr_done)) return e;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  const int tiles = p.M / MLP_BM;
-  const int grid = tiles < cus ? tiles : cus;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), MW_SMEM, s, p, tiles);
-  return idf_launch_status();
-}
-
 // IDF_MLP_MODE: 0 = mlp320_kernel (two waves per SIMD), 1 = mlp320w_kernel (one instruction stream per SIMD)
 #ifndef IDF_MLP_MODE_DEFAULT
 #define IDF_MLP_MODE_DEFAULT 1
 #endif
-int g_mlp_mode = -1;
-inline int mlp_mode() {
-  if (g_mlp_mode < 0) { const char* e = getenv("IDF_MLP_MODE"); g_mlp_mode = e ? (e[0] == '0' ? 0 : 1) : IDF_MLP_MODE_DEFAULT; }
-  return g_mlp_mode;
-}
+MwKnob g_mlp_knob{"IDF_MLP_MODE", IDF_MLP_MODE_DEFAULT};
 
 }  // namespace
 
 // idf_set_tuning(IDF_TUNE_MLP, v): returns the previous mode
-int idf_mlp_set_mode(int v) {
-  const int prev = mlp_mode();
-  g_mlp_mode = v;
-  return prev;
-}
+int idf_mlp_set_mode(int v) { return g_mlp_knob.set(v); }
 
 #ifdef IDF_MLPW_TRACE
 extern "C" int idf_mlpw_trace_read(unsigned long long* host /* [4][12] */) {
@@ -706,6 +661,8 @@ extern "C" int idf_mlp_geglu(const idf_mlp_args* a, void* stream) {
   p.w2p = static_cast<const unsigned short*>(a->w2p); p.ldw2 = a->ldw2; p.b2 = a->b2; p.gate = a->gate;
   p.out = static_cast<unsigned short*>(a->out); p.ldo = a->ldo; p.M = a->M;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (mlp_mode() == 1) return a->dtype == IDF_BF16 ? launch_mlp320w<IDF_BF16>(p, s) : launch_mlp320w<IDF_F16>(p, s);
-  return a->dtype == IDF_BF16 ? launch_mlp320<IDF_BF16>(p, s) : launch_mlp320<IDF_F16>(p, s);
+  const bool bf = a->dtype == IDF_BF16;
+  if (g_mlp_knob.get() == 1)
+    return bf ? mw_row_launch<MlpParams, mlp320w_kernel<IDF_BF16>, MW_SMEM, MLP_BM>(p, s) : mw_row_launch<MlpParams, mlp320w_kernel<IDF_F16>, MW_SMEM, MLP_BM>(p, s);
+  return bf ? mw_row_launch<MlpParams, mlp320_kernel<IDF_BF16>, MLP_SMEM, MLP_BM, 512>(p, s) : mw_row_launch<MlpParams, mlp320_kernel<IDF_F16>, MLP_SMEM, MLP_BM, 512>(p, s);
 }

@@ -1,5 +1,5 @@
-// mw_prims.h -- instruction-level primitives of the one-instruction-stream-per-SIMD kernels (mlp_fused.hip mlp320w_kernel,
-// qkv_fused.hip qkv320w_kernel): every one is a single `asm volatile` statement, so a stream written with them issues in source
+// mw_prims.h -- instruction-level primitives of the one-instruction-stream-per-SIMD kernels (the row-resident kernels, whose
+// shared skeleton is mw_row.h): every one is a single `asm volatile` statement, so a stream written with them issues in source
 // order (the compiler's scheduler clusters pure VALU / LDS operations in front of the MFMAs otherwise), and the registers named
 // in the asm text (AGPR blocks) are invisible to the register allocator.  What the compiler then cannot do for us: s_waitcnt
 // lgkmcnt in front of the first use of an LDS read (mw_wait_lgkm, placed by the stream generators), MFMA -> VALU / AGPR-read

@@ -30,10 +30,7 @@
 // four 16-bit products (c and -mu split hi + lo, 2^-17 each) instead of an fp32 fma per element: measured error against fp64
 // identical to the persistent kernel's (1.66e-3 bf16 / 2.07e-4 fp16 rel-RMS), 0.1 % of the outputs differ by one 16-bit ulp.
 // LDS: 2 x 40 KB ring + 15.5 KB (the c table as 16-bit hi | lo pairs) + 3.75 KB (d) + 1 KB (the waves' rstd tables) + 4 x 8 KB staging = 132 KB.
-#include "gemm_core.h"
-#include "mw_prims.h"
-#include <cstdlib>
-#include <atomic>
+#include "mw_row.h"
 
 using namespace idfcore;
 using namespace idfmw;
@@ -78,42 +75,29 @@ template <int DT>
 __global__ __launch_bounds__(256, 1) void qkv320w_kernel(const QwParams p, const int tiles) {
   asm volatile("" ::: "a0", "a171");               // the asm-owned AGPR block (this is where the kernel descriptor learns its size)
   extern __shared__ __attribute__((aligned(128))) char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, hi = lane >> 5;
+  const RowLane rl = mw_row_lane();
+  const int tid = rl.tid, lane = rl.lane, wave = rl.wave, l31 = rl.l31, hi = rl.hi;
   const int G = gridDim.x;
   const unsigned smem_lds = lds_u32(smem);
 
   QwCtx c;
-  // LDS-DMA roles (mlp_fused.hip): piece (kt, u) = rows 8 (wave + 4 u) .. + 7 of K-tile kt: lane -> row + lane / 8, 16-B slot lane % 8
-  unsigned w1_voff;
-  {
-    const int row = 8 * wave + (lane >> 3);
-    w1_voff = (unsigned)(row * p.ldw + (((lane & 7) ^ ((row >> 1) & 7)) << 3)) * 2u;
-  }
+  // LDS-DMA roles (mw_row.h): piece (kt, u) = rows 8 (wave + 4 u) .. + 7 of K-tile kt
+  const unsigned w1_voff = mw_w1_voff(rl, p.ldw);
   const char* const wg = reinterpret_cast<const char*>(p.w);
   const unsigned w_chunk = (unsigned)(64 * p.ldw * 2);
 #pragma unroll
   for (int u = 0; u < 2; ++u) c.w1b[u] = wg + (size_t)u * (unsigned)(32 * p.ldw * 2);
-  const int sw1 = (l31 >> 1) & 7;
+  const int sw1 = mw_sw1(rl);
   unsigned w1o[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) w1o[i] = smem_lds + (unsigned)(l31 * 128 + (((2 * i + hi) ^ sw1) << 4));
-  // staging slot of the wave (4 KB).  q | k image: [32 tokens][128 B], 16-B slot ^= (row >> 1) & 7; a lane writes 8 B of
-  // slot s = 4 f + q of its token row (+ 8 hi inside the slot), reads back rows lane / 8 + 8 i, slot lane % 8.
+  mw_w1_frag(rl, smem_lds, w1o);
+  // staging slot of the wave (4 KB).  q | k image (mw_row.h): [32 tokens][128 B]; a lane writes slot s = 4 f + q of its token row.
   // V^T image per fragment (4 KB, the slot is 8 KB): [32 channels][128 B = the wave's 64 tokens], same swizzle; a lane of row
   // group r writes slots 4 r + 2 hi, + 1 of its channel row; read back (by the chunk's second item) as the q | k image.
   {
     const unsigned stg = smem_lds + (unsigned)(QW_STG_OFF + wave * 8192);
-    const unsigned base = stg + (unsigned)(l31 * 128 + 8 * hi + (sw1 << 4));
+    const unsigned base = mw_stage_image(rl, stg, p.ldo, c.qr, c.qst);
 #pragma unroll
     for (int s = 0; s < 8; ++s) c.qw[s] = base ^ (unsigned)(16 * s);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = (lane >> 3) + 8 * i;
-      c.qr[i] = stg + (unsigned)(row * 128 + (((lane & 7) ^ ((row >> 1) & 7)) << 4));
-      c.qst[i] = (unsigned)(row * p.ldo * 2 + (lane & 7) * 16);
-    }
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -123,7 +107,7 @@ __global__ __launch_bounds__(256, 1) void qkv320w_kernel(const QwParams p, const
   }
   const unsigned cd_lds = smem_lds + (unsigned)QW_CD_OFF;
 
-  int tile = ((G & 7) == 0) ? (int)(blockIdx.x & 7) * (G >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+  int tile = mw_first_tile(G);
   if (tile >= tiles) return;
 
   // kernel prologue: c | d of all 960 columns into LDS, W chunk 0 into ring slot 0, the first tile's rows and statistics
@@ -257,49 +241,21 @@ __global__ __launch_bounds__(256, 1) void qkv320w_kernel(const QwParams p, const
   }
 }
 
-template <int DT>
-int launch_qkv320w(const QwParams& p, hipStream_t s) {
-  void (*kern)(const QwParams, const int) = qkv320w_kernel<DT>;
-  static std::atomic<unsigned long long> attr_done{0};
-  if (const int e = idf_lds_optin(reinterpret_cast<const void*>(kern), QW_SMEM, attr_done)) return e;
-  const int cus = idf_num_cu();
-  const int tiles = p.M / QW_BM;
-  const int grid = tiles < cus ? tiles : cus;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), QW_SMEM, s, p, tiles);
-  return idf_launch_status();
-}
-
-int g_qkvw_mode = -1;
-inline int qkvw_mode() {
-  if (g_qkvw_mode < 0) { const char* e = getenv("IDF_QKV_ROW"); g_qkvw_mode = e ? (e[0] == '0' ? 0 : 1) : 1; }
-  return g_qkvw_mode;
-}
-
 }  // namespace
 
-int idf_qkvw_set_mode(int v) {
-  const int prev = qkvw_mode();
-  g_qkvw_mode = v;
-  idf_qkv640w_set_mode(v);                         // one knob for both levels
-  return prev;
-}
+MwKnob idf_qkv_row_knob{"IDF_QKV_ROW", 1};          // one knob for both levels (qkv640_fused.hip reads it too)
+int idf_qkvw_set_mode(int v) { return idf_qkv_row_knob.set(v); }
 
 // idf_gemm's fused q | k | v branch tries this first; IDF_BIG_UNSUPPORTED = the shape / epilogue is not this kernel's
 int idf_launch_qkv320w(const idfcore::CoreParams& p, int dtype, hipStream_t s) {
-  if (qkvw_mode() == 0) return IDF_BIG_UNSUPPORTED;
-  if (p.K != QW_C || p.N != QW_N || p.vt_col0 != 2 * QW_C || !p.vt_out || !p.out) return IDF_BIG_UNSUPPORTED;
+  if (idf_qkv_row_knob.get() == 0) return IDF_BIG_UNSUPPORTED;
   // (from two tiles per CU: below, the 256-row tiles quantise badly on 256 CUs and the persistent kernel's 256 x 320 tiles, three
   // per row block, spread better)
-  if ((p.M % QW_BM) || p.M < QW_BM * 2 * idf_num_cu()) return IDF_BIG_UNSUPPORTED;
-  if (p.epi != (IDF_EPI_BIAS | IDF_EPI_LN_ROW) || !p.ln_stats || p.stride_ln_stats || !p.ln_c || !p.bias) return IDF_BIG_UNSUPPORTED;
-  if (dtype != IDF_BF16 && dtype != IDF_F16) return IDF_BIG_UNSUPPORTED;
-  if (p.lda < QW_C || p.ldw < QW_C || p.ldo < 2 * QW_C || p.ld_vt < p.M) return IDF_BIG_UNSUPPORTED;
-  if ((p.lda % 8) || (p.ldw % 8) || (p.ldo % 8) || (p.ld_vt % 8)) return IDF_BIG_UNSUPPORTED;
-  if (!aligned16(p.A) || !aligned16(p.W) || !aligned16(p.out) || !aligned16(p.vt_out) || !aligned16(p.ln_c) || !aligned16(p.bias)) return IDF_BIG_UNSUPPORTED;
-  // 32-bit per-lane offsets: W image, a tile's rows of out, 32 channel rows of V^T
-  if ((long long)QW_N * p.ldw * 2 >= (1ll << 31) || (long long)QW_BM * p.ldo * 2 >= (1ll << 31) || (long long)32 * p.ld_vt * 2 >= (1ll << 31)) return IDF_BIG_UNSUPPORTED;
+  if (!mw_row_eligible(p, dtype, QW_C, QW_N, QW_BM, 2 * QW_C) || !mw_row_vt_eligible(p)) return IDF_BIG_UNSUPPORTED;
+  if (p.vt_col0 != 2 * QW_C || p.epi != (IDF_EPI_BIAS | IDF_EPI_LN_ROW)) return IDF_BIG_UNSUPPORTED;
   QwParams q;
   q.x = p.A; q.ldx = p.lda; q.ln_stats = p.ln_stats; q.w = p.W; q.ldw = p.ldw; q.c = p.ln_c; q.d = p.bias;
   q.out = static_cast<unsigned short*>(p.out); q.ldo = p.ldo; q.vt = p.vt_out; q.ld_vt = p.ld_vt; q.M = p.M;
-  return dtype == IDF_BF16 ? launch_qkv320w<IDF_BF16>(q, s) : launch_qkv320w<IDF_F16>(q, s);
+  return dtype == IDF_BF16 ? mw_row_launch<QwParams, qkv320w_kernel<IDF_BF16>, QW_SMEM, QW_BM>(q, s)
+                           : mw_row_launch<QwParams, qkv320w_kernel<IDF_F16>, QW_SMEM, QW_BM>(q, s);
 }

@@ -199,41 +199,32 @@ def test_attention4w_asm_owned_registers_are_left_alone_by_the_compiler():
         assert not r["stray_accvgpr"] and r["scratch_ops"] == 0 and r["mfma"] > 50, (name, r["stray_accvgpr"][:3], r["scratch_ops"])
 
 
+ROW_KERNELS = [   # (stream generator, prefix of its options in the environment, source file, kernel, MFMAs per instantiation at least)
+    ("gen_mlpw_stream.py", "MW_", "mlp_fused.hip", "mlp320w_kernel", 200),        # x fragments a0..a79, output accumulators a80..a239
+    ("gen_qkvw_stream.py", "QW_", "qkv_fused.hip", "qkv320w_kernel", 200),        # x fragments a0..a159, mean fragments, statistics: a0..a171
+    ("gen_qkv640w_stream.py", "QM_", "qkv640_fused.hip", "qkv640w_kernel", 100),  # x fragments a0..a159, statistics a160:161
+    ("gen_gegluw_stream.py", "GW_", "geglu_fused.hip", "geglu640w_kernel", 100),  # the same block
+]
+
+
 def test_mlp320w_stream_is_current_and_its_registers_are_left_alone():
-    """mlp_fused.hip's one-wave-per-SIMD kernel: (1) the checked-in instruction stream (csrc/mlpw_stream.inc) is what
-    tools/gen_mlpw_stream.py writes with its default options; (2) its asm-owned AGPR block (x fragments a0..a79, output
-    accumulators a80..a239) is not touched by compiler-generated code and the kernel has no scratch, in both element types."""
+    """The row-resident kernels (csrc/mw_row.h), mlp_fused.hip's one-wave-per-SIMD kernel first: (1) the checked-in instruction
+    stream (csrc/*_stream.inc) is what its generator writes with its default options; (2) the asm-owned AGPR block is not touched
+    by compiler-generated code and the kernel has no scratch (a scratch access would also break the counted vmcnt waits), in both
+    element types."""
     import importlib.util
     import subprocess
     import sys
-    env = {k: v for k, v in os.environ.items() if not k.startswith("MW_")}
-    assert subprocess.run([sys.executable, os.path.join(REPO, "tools", "gen_mlpw_stream.py"), "--check"], env=env).returncode == 0
     spec = importlib.util.spec_from_file_location("check_attn4w_isa", os.path.join(REPO, "tools", "check_attn4w_isa.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    rep = mod.check(src=os.path.join(REPO, "instancediffusion_amd", "csrc", "mlp_fused.hip"), kernel="mlp320w_kernel")
-    assert len(rep) == 2, sorted(rep)
-    for name, r in rep.items():
-        assert not r["stray_accvgpr"] and r["scratch_ops"] == 0 and r["mfma"] > 200, (name, r["stray_accvgpr"][:3], r["scratch_ops"])
-    # the same for qkv_fused.hip's row-resident q | k | v kernel (x fragments a0..a159, mean fragments, statistics: a0..a171); a
-    # scratch access there would also break its counted vmcnt waits
-    assert subprocess.run([sys.executable, os.path.join(REPO, "tools", "gen_qkvw_stream.py"), "--check"], env={k: v for k, v in os.environ.items() if not k.startswith("QW_")}).returncode == 0
-    rep = mod.check(src=os.path.join(REPO, "instancediffusion_amd", "csrc", "qkv_fused.hip"), kernel="qkv320w_kernel")
-    assert len(rep) == 2, sorted(rep)
-    for name, r in rep.items():
-        assert not r["stray_accvgpr"] and r["scratch_ops"] == 0 and r["mfma"] > 200, (name, r["stray_accvgpr"][:3], r["scratch_ops"])
-    # ... qkv640_fused.hip (the C = 640 level's q | k | v projection on geglu_fused.hip's skeleton)
-    assert subprocess.run([sys.executable, os.path.join(REPO, "tools", "gen_qkv640w_stream.py"), "--check"], env={k: v for k, v in os.environ.items() if not k.startswith("QM_")}).returncode == 0
-    rep = mod.check(src=os.path.join(REPO, "instancediffusion_amd", "csrc", "qkv640_fused.hip"), kernel="qkv640w_kernel")
-    assert len(rep) == 2, sorted(rep)
-    for name, r in rep.items():
-        assert not r["stray_accvgpr"] and r["scratch_ops"] == 0 and r["mfma"] > 100, (name, r["stray_accvgpr"][:3], r["scratch_ops"])
-    # ... and geglu_fused.hip's row-resident GEGLU projection (x fragments a0..a159, statistics a160:161)
-    assert subprocess.run([sys.executable, os.path.join(REPO, "tools", "gen_gegluw_stream.py"), "--check"], env={k: v for k, v in os.environ.items() if not k.startswith("GW_")}).returncode == 0
-    rep = mod.check(src=os.path.join(REPO, "instancediffusion_amd", "csrc", "geglu_fused.hip"), kernel="geglu640w_kernel")
-    assert len(rep) == 2, sorted(rep)
-    for name, r in rep.items():
-        assert not r["stray_accvgpr"] and r["scratch_ops"] == 0 and r["mfma"] > 100, (name, r["stray_accvgpr"][:3], r["scratch_ops"])
+    for gen, prefix, src, kernel, mfma_floor in ROW_KERNELS:
+        env = {k: v for k, v in os.environ.items() if not k.startswith(prefix)}
+        assert subprocess.run([sys.executable, os.path.join(REPO, "tools", gen), "--check"], env=env).returncode == 0, gen
+        rep = mod.check(src=os.path.join(REPO, "instancediffusion_amd", "csrc", src), kernel=kernel)
+        assert len(rep) == 2, sorted(rep)
+        for name, r in rep.items():
+            assert not r["stray_accvgpr"] and r["scratch_ops"] == 0 and r["mfma"] > mfma_floor, (name, r["stray_accvgpr"][:3], r["scratch_ops"])
 
 
 def test_schema_matches_reference():

@@ -1,7 +1,13 @@
 """Safety check of attention4w.hip's asm-owned AGPR block.  The kernel keeps its O^T accumulators, Q and V^T fragments in AGPRs
 that are NAMED in inline asm: the register allocator knows them only as clobbers, so a compiler-generated v_accvgpr_* (an AGPR
 used as VGPR spill space) or any scratch access inside attn4w_kernel would silently corrupt them.  This compiles the file to
-assembly with the library's flags and fails when either appears.      python tools/check_attn4w_isa.py [extra hipcc flags]"""
+assembly with the library's flags and fails when either appears.      python tools/check_attn4w_isa.py [extra hipcc flags]
+
+The row-resident kernels (mlp320w / qkv320w / qkv640w / geglu640w) depend on more than that: their generated streams wait with
+counted vmcnt / lgkmcnt, so the ORDER of every memory, LDS, MFMA and wait instruction the compiler emits around the streams is
+part of their correctness.  `skeleton()` extracts that order; to show that an edit of those files left it alone:
+    python tools/check_attn4w_isa.py --compare OLD_TREE NEW_TREE"""
+import collections
 import os
 import re
 import subprocess
@@ -13,15 +19,69 @@ SRC = os.path.join(ROOT, "instancediffusion_amd", "csrc", "attention4w.hip")
 FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-gpu-rdc -Wno-unused-result -mllvm -amdgpu-mfma-vgpr-form".split()
 
 
-def check(extra=(), src=SRC, kernel="attn4w_kernel"):
-    """src / kernel: the same scan for another file with asm-owned AGPRs (mlp_fused.hip's mlp320w_kernel)"""
+ROW_KERNELS = [("mlp_fused.hip", "mlp320w_kernel"), ("mlp_fused.hip", "mlp320_kernel"), ("qkv_fused.hip", "qkv320w_kernel"),
+               ("qkv640_fused.hip", "qkv640w_kernel"), ("geglu_fused.hip", "geglu640w_kernel")]
+ORDERED = ("global_", "buffer_", "flat_", "scratch_", "ds_", "s_load", "s_barrier", "v_mfma", "v_accvgpr")
+DESCRIPTOR = ("next_free_vgpr", "next_free_sgpr", "accum_offset", "private_segment_fixed_size", "group_segment_fixed_size")
+
+
+def listing(src, extra=()):
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "a.s")
         subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *extra, "--cuda-device-only", "-S", src, "-o", out], check=True,
-                       cwd=os.path.dirname(src))
-        txt = open(out).read()
+                       cwd=os.path.dirname(src), stderr=subprocess.DEVNULL)
+        return open(out).read()
+
+
+def bodies(txt, kernel):
+    """[(mangled name, text from the kernel's label to its s_endpgm)], one per instantiation"""
+    return re.findall(r"\n(_ZN\S*" + kernel + r"\S*):[^\n]*\n(.*?)\n\ts_endpgm", txt, flags=re.S)
+
+
+def skeleton(src, kernel, extra=()):
+    """per instantiation `kernel<DT>`: seq = the ordered memory / LDS / MFMA / AGPR mnemonics and every s_waitcnt WITH its
+    operands; mnemonics = the multiset of all instructions; desc = the kernel descriptor's register and segment sizes"""
+    txt = listing(src, extra)
+    out = {}
+    for name, body in bodies(txt, kernel):
+        seq, mnem = [], collections.Counter()
+        for line in body.split("\n"):
+            t = line.split(";")[0].strip()
+            if not t or t.startswith(".") or t.endswith(":"):
+                continue
+            m = t.split()[0]
+            mnem[m] += 1
+            if m == "s_waitcnt":
+                seq.append(" ".join(t.split()))
+            elif m.startswith(ORDERED):
+                seq.append(m)
+        blk = re.search(r"\.amdhsa_kernel " + re.escape(name) + r"\n(.*?)\.end_amdhsa_kernel", txt, flags=re.S).group(1)
+        desc = {k: int(re.search(r"\.amdhsa_" + k + r" (\d+)", blk).group(1)) for k in DESCRIPTOR}
+        out[kernel + "<" + re.search(r"ILi(\d+)E", name).group(1) + ">"] = dict(seq=seq, mnemonics=mnem, desc=desc)
+    return out
+
+
+def compare(old_tree, new_tree):
+    """0 when every row kernel of new_tree has the ordered sequence and the descriptor of old_tree's; prints the instructions
+    added / removed where the mnemonic multisets differ (address arithmetic may; nothing else should)"""
+    bad = False
+    for f, kernel in ROW_KERNELS:
+        a, b = (skeleton(os.path.join(t, "instancediffusion_amd", "csrc", f), kernel) for t in (old_tree, new_tree))
+        bad |= sorted(a) != sorted(b) or not a
+        for k in sorted(set(a) & set(b)):
+            same_seq, same_desc = a[k]["seq"] == b[k]["seq"], a[k]["desc"] == b[k]["desc"]
+            add, rem = b[k]["mnemonics"] - a[k]["mnemonics"], a[k]["mnemonics"] - b[k]["mnemonics"]
+            print(f"{k}: {len(b[k]['seq'])} ordered entries {'same' if same_seq else 'DIFFER'}; descriptor {b[k]['desc']} "
+                  f"{'same' if same_desc else 'DIFFERS from ' + str(a[k]['desc'])}; {sum(b[k]['mnemonics'].values())} instructions"
+                  f" added {dict(add)} removed {dict(rem)}")
+            bad |= not (same_seq and same_desc)
+    return 1 if bad else 0
+
+
+def check(extra=(), src=SRC, kernel="attn4w_kernel"):
+    """src / kernel: the same scan for another file with asm-owned AGPRs (mlp_fused.hip's mlp320w_kernel)"""
     report = {}
-    for name, body in re.findall(r"\n(_ZN\S*" + kernel + r"\S*):[^\n]*\n(.*?)\n\ts_endpgm", txt, flags=re.S):
+    for name, body in bodies(listing(src, extra), kernel):
         in_asm, stray, scratch, mfma = False, [], 0, 0
         for line in body.split("\n"):
             t = line.strip()
@@ -40,6 +100,8 @@ def check(extra=(), src=SRC, kernel="attn4w_kernel"):
 
 
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["--compare"]:
+        sys.exit(compare(os.path.abspath(sys.argv[2]), os.path.abspath(sys.argv[3])))
     rep = check(sys.argv[1:])
     bad = False
     for k, v in rep.items():

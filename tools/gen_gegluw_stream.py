@@ -16,27 +16,7 @@ tile's rows BEFORE its stores).
 
     python tools/gen_gegluw_stream.py            # rewrites the .inc (checked in; CPU test in tests/test_capi.py)
 """
-import os
-
-from mw_streamgen import ARGS, finish, header, schedule
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "instancediffusion_amd", "csrc", "gegluw_stream.inc")
-LA = int(os.environ.get("GW_LA", 3))
-PRE_DMA = int(os.environ.get("GW_PRE_DMA", 3))
-MAXV = int(os.environ.get("GW_MAXV", 6))
-NO_EPI = os.environ.get("GW_NO_EPI") == "1"       # timing experiments (wrong results)
-NO_DMA = os.environ.get("GW_NO_DMA") == "1"
-
-
-def mf_items():
-    out = []
-    for ks in range(40):
-        name = f"w_{ks}"
-        first = "true" if ks < 2 else "false"
-        out.append((f"mw_mf1<DT, {ks}, {first}>(accN[{ks & 1}], {name});", name,
-                    f"const u32x4 {name} = mw_lds128<{(ks >> 2) * 4096}>(c.w1a[{ks & 3}]);"))
-    return out
+from mw_streamgen import XLOAD640, Gen, dma_pieces640, mf_items640
 
 
 def epilogue(store):
@@ -101,26 +81,14 @@ def epilogue(store):
     return it
 
 
-def dma_pieces():
-    return [f"mw_dma<{kt * 4096}, {kt * 128}>(c.w1dst, c.w1_vj, c.wb);" for kt in range(10)]
-
-
-def build(name, epi, mf, store, top=True, xload=False):
-    decl = f"template <int DT, int VMC> __device__ __forceinline__ void {name}({ARGS.format(ctx='GwCtx')})"
-    xl = ("if (c.has_next) { mw_static_for<40>([&](auto kc) { mw_load_x2<decltype(kc)::value, decltype(kc)::value>(c.xnext); }); "
-          "asm volatile(\"global_load_dwordx2 a[160:161], %0, off\" ::\"v\"(c.snext) : \"memory\"); }")
-    return schedule(decl, mf_items() if mf else [], dma_pieces() if (mf and not NO_DMA) else [],
-                    epilogue(store) if (epi and not NO_EPI) else [], LA, PRE_DMA, MAXV,
-                    top="mw_wait_vm_barrier<VMC>();" if top else None, xload=xl if xload else None)
-
-
 def main():
-    parts = header("gen_gegluw_stream.py", LA, PRE_DMA, MAXV)
-    parts.append(build("gw_pro", False, True, False, top=False))
-    parts.append(build("gw_step", True, True, False))
-    parts.append(build("gw_step_st", True, True, True))
-    parts.append(build("gw_last", True, False, True, xload=True))
-    finish(parts, OUT)
+    g = Gen("gen_gegluw_stream.py", "gegluw_stream.inc", "GW", "GwCtx", 3, 3, 6, xload=XLOAD640)
+    mf, dma = mf_items640(), dma_pieces640()
+    g.add("gw_pro", mf, dma, [], top=False)
+    g.add("gw_step", mf, dma, epilogue(False))
+    g.add("gw_step_st", mf, dma, epilogue(True))
+    g.add("gw_last", [], [], epilogue(True), xload=True)
+    g.finish()
 
 
 if __name__ == "__main__":

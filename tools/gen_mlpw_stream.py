@@ -15,13 +15,19 @@ One iteration j of a tile (40 chunks of 32 intermediate columns), "gap" = the is
 Variants: 11 (steady state), 01 (j = 0: no second product yet), 10 (j = 39: no next first product), drain (j = 40: second
 product only), pro (first product of chunk 0 only).
 
+The LDS-read counter (`Stream`), the file header and the command line (-o FILE, --check) are tools/mw_streamgen.py's.  The
+scheduling loop below is NOT folded into its `schedule()`: this kernel has two MFMA parts per step, sorts the constant reads
+ahead of the W reads of the same gap, measures the look-ahead window from the gap behind the MFMA, allows 14 outstanding reads
+(13 there) and carries the STAGGER / TRACE / NO_MFMA experiment switches -- a flag per quirk in `schedule()` would cost more
+than this loop does, and the checked-in stream has to stay byte-identical.
+
     python tools/gen_mlpw_stream.py            # rewrites the .inc (checked in; CPU test test_mlpw_stream_is_current)
 """
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "instancediffusion_amd", "csrc", "mlpw_stream.inc")
+from mw_streamgen import Stream, csrc, finish, header
+
+OUT = csrc("mlpw_stream.inc")
 
 LA = int(os.environ.get("MW_LA", 3))            # gaps of lookahead of an LDS read in front of its consumer
 PRE_DMA = int(os.environ.get("MW_PRE_DMA", 3))   # LDS-DMA pieces between the top barrier's first reads and the first MFMA (they cover the read latency)
@@ -37,7 +43,6 @@ TRACE = os.environ.get("MW_TRACE") == "1"        # s_memtime marks at the segmen
 class Read:
     def __init__(self, name, expr, need):
         self.name, self.expr, self.need = name, expr, need
-        self.seq = None
 
 
 def valu_half(h):
@@ -188,33 +193,19 @@ def build(name, g2, g1, valu, dma, top=True):
                 cr[rd.name] = rd
                 reads.append(rd)
     reads.sort(key=lambda r: (r.need, 0 if r.name.startswith("c") else 1))
-    for i, r in enumerate(reads):
-        r.seq = i
-    byname = {r.name: r for r in reads}
 
-    lines = []
-    state = dict(issued=0, done=0)
+    stream = Stream()                          # (the reads are its only LDS operations: issued in the FIFO order of `reads`)
+    lines, wait_for = stream.lines, stream.wait
 
     def issue_upto(gap):
         # FIFO; a constant read goes out at most 2 gaps ahead (8 of them at once: the lgkmcnt field counts to 15)
-        while state["issued"] < len(reads):
-            r = reads[state["issued"]]
+        while stream.issued < len(reads):
+            r = reads[stream.issued]
             ahead = min(LA, 2) if r.name.startswith("c") else LA
-            if r.need - ahead > gap - LA or state["issued"] - state["done"] >= 14:
+            if r.need - ahead > gap - LA or stream.issued - stream.done >= 14:
                 break
             ty = "f32x4" if r.name.startswith("c") else "u32x4"
-            lines.append(f"  const {ty} {r.name} = {r.expr};")
-            state["issued"] += 1
-
-    def wait_for(rname):
-        s = byname[rname].seq
-        if s < state["done"]:
-            return
-        assert s < state["issued"], (name, rname)
-        n = state["issued"] - s - 1
-        assert 0 <= n <= 15, (name, rname, n)
-        lines.append(f"  mw_wait_lgkm<{n}>();")
-        state["done"] = s + 1
+            stream.lds(f"const {ty} {r.name} = {r.expr};", r.name)
 
     args = "f32x16 (&accC)[2], f32x16 (&accN)[2], const u32x4 (&hP)[2], u32x4 (&hC)[2], const MwCtx& c"
     lines.append(f"template <int DT> __device__ __forceinline__ void {name}({args}) {{")
@@ -261,7 +252,7 @@ def build(name, g2, g1, valu, dma, top=True):
         for r in needs:
             wait_for(r)
         lines.append("  " + vs)
-    assert state["issued"] == len(reads)
+    assert stream.issued == len(reads)
     if tr:
         lines.append("  MW_TR_MARK(6)")
         lines.append("  MW_TR_END")
@@ -270,22 +261,13 @@ def build(name, g2, g1, valu, dma, top=True):
 
 
 def main():
-    parts = ["// GENERATED by tools/gen_mlpw_stream.py -- do not edit; see that script for the schedule rules.",
-             f"// LA = {LA} gaps of LDS-read lookahead, {PRE_DMA} LDS-DMA pieces in front of the first MFMA.", ""]
+    parts = header("gen_mlpw_stream.py", LA, PRE_DMA)
     parts.append(build("mw_body_11", True, True, True, True))
     parts.append(build("mw_body_01", False, True, True, True))
     parts.append(build("mw_body_10", True, False, True, True))
     parts.append(build("mw_drain", True, False, False, False))
     parts.append(build("mw_pro", False, True, False, False, top=False))
-    txt = "\n\n".join(parts) + "\n"
-    if "-o" in sys.argv:
-        open(sys.argv[sys.argv.index("-o") + 1], "w").write(txt)
-        return
-    if "--check" in sys.argv:
-        cur = open(OUT).read() if os.path.exists(OUT) else ""
-        sys.exit(0 if cur == txt else 1)
-    open(OUT, "w").write(txt)
-    print("wrote", OUT, len(txt.split("\n")), "lines")
+    finish(parts, OUT)
 
 
 if __name__ == "__main__":

@@ -15,28 +15,7 @@ qm_vv, qm_last (epilogue of the last V chunk; it also fetches the next tile's ro
 
     python tools/gen_qkv640w_stream.py            # rewrites the .inc (checked in; CPU test in tests/test_capi.py)
 """
-import os
-
-from mw_streamgen import ARGS, finish, header, schedule
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "instancediffusion_amd", "csrc", "qkv640w_stream.inc")
-LA = int(os.environ.get("QM_LA", 3))
-PRE_DMA = int(os.environ.get("QM_PRE_DMA", 3))
-MAXV = int(os.environ.get("QM_MAXV", 6))
-NO_EPI = os.environ.get("QM_NO_EPI") == "1"       # timing experiments (wrong results)
-NO_DMA = os.environ.get("QM_NO_DMA") == "1"
-
-
-def mf_items(kind):
-    fn = "mw_mf1" if kind == "q" else "mw_mf1t"
-    out = []
-    for ks in range(40):
-        name = f"w_{ks}"
-        first = "true" if ks < 2 else "false"
-        out.append((f"{fn}<DT, {ks}, {first}>(accN[{ks & 1}], {name});", name,
-                    f"const u32x4 {name} = mw_lds128<{(ks >> 2) * 4096}>(c.w1a[{ks & 3}]);"))
-    return out
+from mw_streamgen import XLOAD640, Gen, dma_pieces640, mf_items640
 
 
 def epi_q(store):
@@ -99,29 +78,16 @@ def epi_v():
     return it
 
 
-def dma_pieces():
-    return [f"mw_dma<{kt * 4096}, {kt * 128}>(c.w1dst, c.w1_vj, c.wb);" for kt in range(10)]
-
-
-def build(name, epi, mf, store, top=True, xload=False):
-    """epi: None / "q" / "v"; mf: None / "q" / "v" """
-    decl = f"template <int DT, int VMC> __device__ __forceinline__ void {name}({ARGS.format(ctx='QmCtx')})"
-    xl = ("if (c.has_next) { mw_static_for<40>([&](auto kc) { mw_load_x2<decltype(kc)::value, decltype(kc)::value>(c.xnext); }); "
-          "asm volatile(\"global_load_dwordx2 a[160:161], %0, off\" ::\"v\"(c.snext) : \"memory\"); }")
-    items = (epi_q(store) if epi == "q" else epi_v()) if (epi and not NO_EPI) else []
-    return schedule(decl, mf_items(mf) if mf else [], dma_pieces() if (mf and not NO_DMA) else [], items, LA, PRE_DMA, MAXV,
-                    top="mw_wait_vm_barrier<VMC>();" if top else None, xload=xl if xload else None)
-
-
 def main():
-    parts = header("gen_qkv640w_stream.py", LA, PRE_DMA, MAXV)
-    parts.append(build("qm_pro", None, "q", False, top=False))
-    parts.append(build("qm_qq", "q", "q", False))
-    parts.append(build("qm_qq_st", "q", "q", True))
-    parts.append(build("qm_qv_st", "q", "v", True))
-    parts.append(build("qm_vv", "v", "v", True))
-    parts.append(build("qm_last", "v", None, True, xload=True))
-    finish(parts, OUT)
+    g = Gen("gen_qkv640w_stream.py", "qkv640w_stream.inc", "QM", "QmCtx", 3, 3, 6, xload=XLOAD640)
+    mfq, mfv, dma = mf_items640("mw_mf1"), mf_items640("mw_mf1t"), dma_pieces640()
+    g.add("qm_pro", mfq, dma, [], top=False)
+    g.add("qm_qq", mfq, dma, epi_q(False))
+    g.add("qm_qq_st", mfq, dma, epi_q(True))
+    g.add("qm_qv_st", mfv, dma, epi_q(True))
+    g.add("qm_vv", mfv, dma, epi_v())
+    g.add("qm_last", [], [], epi_v(), xload=True)
+    g.finish()
 
 
 if __name__ == "__main__":

@@ -18,15 +18,8 @@ rows of 128 B, stored by the second item of a chunk).  Variants: pro (MFMA of it
 """
 import os
 
-from mw_streamgen import ARGS, finish, header, schedule
+from mw_streamgen import Gen
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "instancediffusion_amd", "csrc", "qkvw_stream.inc")
-LA = int(os.environ.get("QW_LA", 3))
-PRE_DMA = int(os.environ.get("QW_PRE_DMA", 2))
-MAXV = int(os.environ.get("QW_MAXV", 6))          # epilogue statements per MFMA gap at most; the rest trails
-NO_EPI = os.environ.get("QW_NO_EPI") == "1"       # timing experiments (wrong results)
-NO_DMA = os.environ.get("QW_NO_DMA") == "1"
 NO_STORE = os.environ.get("QW_NO_STORE", "")      # "q" / "v" / "qv": the q | k / V^T stores left out (timing experiments)
 
 
@@ -119,26 +112,22 @@ def dma_pieces():
     return [f"if constexpr (RGM == 0) mw_dma<{kt * 8192 + u * 4096}, {kt * 128}>(c.w1dst, c.w1_vj, c.w1b[{u}]);" for kt in range(5) for u in range(2)]
 
 
-def build(name, epi, mf, top=True, xload=False):
-    """epi: None / "q" / "v1" / "v2" (first / second item of a V chunk); mf: None / "q" / "v" """
-    decl = f"template <int DT, int VMC, int RGM> __device__ __forceinline__ void {name}({ARGS.format(ctx='QwCtx')})"
-    xl = ("if (c.has_next) { mw_static_for<20>([&](auto kc) { mw_load_x2<decltype(kc)::value, decltype(kc)::value>(c.xnext); "
-          "mw_load_x2<20 + decltype(kc)::value, decltype(kc)::value>(c.xnext2); }); "
-          "asm volatile(\"global_load_dwordx2 a[168:169], %0, off\\n\\tglobal_load_dwordx2 a[170:171], %0, off offset:256\" ::\"v\"(c.snext) : \"memory\"); }")
-    items = (epi_q() if epi == "q" else epi_v(epi == "v2")) if (epi and not NO_EPI) else []
-    return schedule(decl, mf_items(mf) if mf else [], dma_pieces() if (mf and not NO_DMA) else [], items, LA, PRE_DMA, MAXV,
-                    top="if constexpr (RGM == 0) mw_wait_vm_barrier<VMC>();" if top else None, xload=xl if xload else None)
+XLOAD = ("if (c.has_next) { mw_static_for<20>([&](auto kc) { mw_load_x2<decltype(kc)::value, decltype(kc)::value>(c.xnext); "
+         "mw_load_x2<20 + decltype(kc)::value, decltype(kc)::value>(c.xnext2); }); "
+         "asm volatile(\"global_load_dwordx2 a[168:169], %0, off\\n\\tglobal_load_dwordx2 a[170:171], %0, off offset:256\" ::\"v\"(c.snext) : \"memory\"); }")
 
 
 def main():
-    parts = header("gen_qkvw_stream.py", LA, PRE_DMA, MAXV)
-    parts.append(build("qw_pro", None, "q", top=False))
-    parts.append(build("qw_qq", "q", "q"))
-    parts.append(build("qw_qv", "q", "v"))
-    parts.append(build("qw_vv1", "v1", "v"))        # epilogue of a chunk's first V item (row group 0): RGM = 1 only
-    parts.append(build("qw_vv0", "v2", "v"))        # epilogue of its second item: RGM = 0 only
-    parts.append(build("qw_v_", "v2", None, xload=True))
-    finish(parts, OUT)
+    g = Gen("gen_qkvw_stream.py", "qkvw_stream.inc", "QW", "QwCtx", 3, 2, 6, tmpl="int DT, int VMC, int RGM",
+            top="if constexpr (RGM == 0) mw_wait_vm_barrier<VMC>();", xload=XLOAD)
+    mfq, mfv, dma = mf_items("q"), mf_items("v"), dma_pieces()
+    g.add("qw_pro", mfq, dma, [], top=False)
+    g.add("qw_qq", mfq, dma, epi_q())
+    g.add("qw_qv", mfv, dma, epi_q())
+    g.add("qw_vv1", mfv, dma, epi_v(False))           # epilogue of a chunk's first V item (row group 0): RGM = 1 only
+    g.add("qw_vv0", mfv, dma, epi_v(True))            # epilogue of its second item: RGM = 0 only
+    g.add("qw_v_", [], [], epi_v(True), xload=True)
+    g.finish()
 
 
 if __name__ == "__main__":

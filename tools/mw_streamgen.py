@@ -1,5 +1,6 @@
 """The scheduler shared by the generators of the row kernels' instruction streams (gen_qkvw_stream.py, gen_qkv640w_stream.py,
-gen_gegluw_stream.py -> instancediffusion_amd/csrc/*_stream.inc; gen_mlpw_stream.py, the first of the family, keeps its own).
+gen_gegluw_stream.py -> instancediffusion_amd/csrc/*_stream.inc; gen_mlpw_stream.py, the first of the family, keeps its own
+scheduling loop and uses the `Stream` counter, `header` and `finish` of this module).
 
 A stream is ONE wave's program for one pipeline step: every statement becomes an `asm volatile` primitive of csrc/mw_prims.h, so
 the order written here is the order issued.  The rules:
@@ -14,6 +15,11 @@ the order written here is the order issued.  The rules:
     trails the last MFMA
 An epilogue is a list of (kind, code, needs, defines): kind 'r' a hoistable LDS read, 'l' an LDS operation that stays in place
 (a write, or the read-back of a staging image), 's' any other statement; `needs` names the reads it consumes.
+
+`Gen` is what a generator script is made of besides its epilogues: the options <PREFIX>_LA / _PRE_DMA / _MAXV (and the timing
+experiments _NO_EPI / _NO_DMA = 1: wrong results) from the environment, the declaration of a stream function, and the file.
+`mf_items640` / `dma_pieces640` / `XLOAD640` are the MFMA backbone, the LDS-DMA pieces and the next-tile fetch of the K = 640
+kernels (csrc/mw_row.h Row640: one 32 x 32 fragment, 40 k-steps on two accumulators, ten K-tiles per chunk).
 """
 import os
 import sys
@@ -128,9 +134,10 @@ def schedule(decl, mfs, pieces, items, la, pre_dma, maxv, top=None, xload=None):
     return "\n".join(st.lines)
 
 
-def header(script, la, pre_dma, maxv):
+def header(script, la, pre_dma, maxv=None):
+    tail = f", <= {maxv} epilogue statements per gap." if maxv is not None else "."
     return [f"// GENERATED by tools/{script} -- do not edit; see that script for the schedule rules.",
-            f"// LA = {la} gaps of LDS-read lookahead, {pre_dma} LDS-DMA pieces in front of the first MFMA, <= {maxv} epilogue statements per gap.", ""]
+            f"// LA = {la} gaps of LDS-read lookahead, {pre_dma} LDS-DMA pieces in front of the first MFMA{tail}", ""]
 
 
 def finish(parts, out):
@@ -144,3 +151,47 @@ def finish(parts, out):
         sys.exit(0 if cur == txt else 1)
     open(out, "w").write(txt)
     print("wrote", out, len(txt.split("\n")), "lines")
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def csrc(name):
+    return os.path.join(ROOT, "instancediffusion_amd", "csrc", name)
+
+
+class Gen:
+    def __init__(self, script, out, prefix, ctx, la, pre_dma, maxv, tmpl="int DT, int VMC", top="mw_wait_vm_barrier<VMC>();", xload=None):
+        env = os.environ
+        self.script, self.out, self.ctx, self.tmpl, self.top, self.xload = script, csrc(out), ctx, tmpl, top, xload
+        self.LA, self.PRE_DMA, self.MAXV = (int(env.get(f"{prefix}_{k}", d)) for k, d in (("LA", la), ("PRE_DMA", pre_dma), ("MAXV", maxv)))
+        self.NO_EPI, self.NO_DMA = env.get(f"{prefix}_NO_EPI") == "1", env.get(f"{prefix}_NO_DMA") == "1"
+        self.parts = header(script, self.LA, self.PRE_DMA, self.MAXV)
+
+    def add(self, name, mfs, pieces, items, top=True, xload=False):
+        """one stream: the MFMAs `mfs` with their `pieces`, the epilogue `items` of the work item before"""
+        decl = f"template <{self.tmpl}> __device__ __forceinline__ void {name}({ARGS.format(ctx=self.ctx)})"
+        self.parts.append(schedule(decl, mfs, [] if self.NO_DMA else pieces, [] if self.NO_EPI else items, self.LA, self.PRE_DMA, self.MAXV,
+                                   top=self.top if top else None, xload=self.xload if xload else None))
+
+    def finish(self):
+        finish(self.parts, self.out)
+
+
+def mf_items640(fn="mw_mf1"):
+    """fn: mw_mf1 (a lane owns a token) or mw_mf1t (operands swapped: a lane owns a W row)"""
+    out = []
+    for ks in range(40):
+        name = f"w_{ks}"
+        first = "true" if ks < 2 else "false"
+        out.append((f"{fn}<DT, {ks}, {first}>(accN[{ks & 1}], {name});", name,
+                    f"const u32x4 {name} = mw_lds128<{(ks >> 2) * 4096}>(c.w1a[{ks & 3}]);"))
+    return out
+
+
+def dma_pieces640():
+    return [f"mw_dma<{kt * 4096}, {kt * 128}>(c.w1dst, c.w1_vj, c.wb);" for kt in range(10)]
+
+
+XLOAD640 = ("if (c.has_next) { mw_static_for<40>([&](auto kc) { mw_load_x2<decltype(kc)::value, decltype(kc)::value>(c.xnext); }); "
+            "asm volatile(\"global_load_dwordx2 a[160:161], %0, off\" ::\"v\"(c.snext) : \"memory\"); }")

@@ -163,7 +163,7 @@ int main(int argc, char** argv) {
       const double flop = 2.0 * Mt * ((double)N1 * C + (double)C * H);
       printf("    M %6d: fused %8.1f us (%6.1f TF)   two gemms %8.1f us (%6.1f TF)   %+5.1f %%\n", Mt, tf[1], flop / tf[1] * 1e-6, tg[1],
              flop / tg[1] * 1e-6, (tg[1] / tf[1] - 1.0) * 100.0);
-      // a -DIDF_MLPW_TRACE build (tools/build_mlpw_variant.sh <name> MW_TRACE=1 -- -DIDF_MLPW_TRACE): the stream kernel's trace
+      // a -DIDF_MLPW_TRACE build (tools/build_row_variant.sh mlpw <name> MW_TRACE=1 -- -DIDF_MLPW_TRACE): the stream kernel's trace
       if (auto rdw = (int (*)(unsigned long long*))dlsym(RTLD_DEFAULT, "idf_mlpw_trace_read")) {
         fused(Mt, dout); hipDeviceSynchronize();
         unsigned long long tr[4][12];
