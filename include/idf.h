@@ -202,6 +202,13 @@ typedef struct {
   float* gn_partial;
 } idf_conv3x3_args;
 int idf_conv3x3(const idf_conv3x3_args* a, void* stream);
+/* The VAE encoder's Downsample (ldm/modules/diffusionmodules/model.py:60-79): zero-pad RIGHT AND BOTTOM only, then 3x3 stride 2
+ * without padding -- out[yo][xo] = sum w[ky][kx] x[2 yo + ky][2 xo + kx], rows / columns >= Hin / Win read zero,
+ * Ho = (Hin - 2) / 2 + 1 (likewise Wo).  The same argument block, weight layout, epilogue flags, split-K workspace and gn_partial
+ * contract as idf_conv3x3 (one launcher, the window origin moved by one pixel); stride must be 2, upsample 0, Hin, Win >= 2,
+ * anything else is IDF_E_ARG before any launch.  Added within ABI 5: a new symbol only, no struct or existing entry point
+ * changed, so callers built against the earlier ABI 5 header are unaffected. */
+int idf_conv3x3_down(const idf_conv3x3_args* a, void* stream);
 
 /* first conv 4->C directly from the fp32 NCHW latent (openaimodel.py:371, :469-480): out NHWC 16-bit */
 int idf_conv_in(const float* x_nchw, const float* w /*[C][Cin][3][3]*/, const float* bias, void* out,
@@ -307,6 +314,16 @@ int idf_softmax_rows(const float* s, void* p, long long rows, int n, long long l
                      int dtype, void* stream);
 int idf_pointwise_nchw(const float* x, const float* w /*[Cout][Cin]*/, const float* bias, float* out, int B, int Cin,
                        int Cout, long long HW, float in_scale, void* stream);
+
+/* ---- VAE encoder tail (ldm/models/autoencoder.py:27-31, ldm/modules/distributions/distributions.py:24-37) -------------
+ * One launch for everything behind the encoder's conv_out: h = fp32 NCHW [B, C2, H, W] (what IDF_EPI_OUT_NCHW writes),
+ * moments = quant_conv(h) with w [2E][C2], bias f32 [2E] or NULL (C2 <= 16, 2E <= 16), (mean | logvar) = channel halves,
+ * logvar clamped to [-30, 20], z[B, E, H, W] = (mean + exp(0.5 logvar) * noise) * scale in fp32.  noise == NULL gives the mode
+ * (z = mean * scale).  moments != NULL additionally receives [B, 2E, H, W] (mean | clamped logvar).  HW = H * W.  (The encoder's
+ * other layers are idf_conv_in / idf_groupnorm / idf_conv3x3 / idf_conv3x3_down / idf_gemm / idf_softmax_rows calls.)
+ * Added within ABI 5 like idf_conv3x3_down: a new symbol only. */
+int idf_vae_posterior(const float* h, const float* w /*[2E][C2]*/, const float* bias, const float* noise, float scale, float* z,
+                      float* moments, int B, int C2, int E, long long HW, void* stream);
 
 /* ---- layout helpers ---------------------------------------------------------------------------------------*/
 int idf_cast_f32_to_16(const float* x, void* out, long long n, int dtype, void* stream);

@@ -65,6 +65,7 @@ SYMBOLS = {
     "idf_get_stat": (ll, [ci]),
     "idf_gemm": (ci, [C.POINTER(GemmArgs), vp]),
     "idf_conv3x3": (ci, [C.POINTER(ConvArgs), vp]),
+    "idf_conv3x3_down": (ci, [C.POINTER(ConvArgs), vp]),
     "idf_mlp_geglu": (ci, [C.POINTER(MlpArgs), vp]),
     "idf_conv_in": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
     "idf_attention": (ci, [C.POINTER(AttnArgs), vp]),
@@ -86,6 +87,7 @@ SYMBOLS = {
     "idf_cast_f32_to_16": (ci, [vp, vp, ll, ci, vp]),
     "idf_softmax_rows": (ci, [vp, vp, ll, ci, ll, ll, cf, ci, vp]),
     "idf_pointwise_nchw": (ci, [vp, vp, vp, vp, ci, ci, ci, ll, cf, vp]),
+    "idf_vae_posterior": (ci, [vp, vp, vp, vp, cf, vp, vp, ci, ci, ci, ll, vp]),
 }
 
 _lib = None

@@ -664,7 +664,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
         const int hw = p.Ho * p.Wo;
         const int b = m / hw, rem = m - b * hw;
         const int yo = rem / p.Wo, xo = rem - yo * p.Wo;
-        const int y0 = yo * p.stride - 1, x0 = xo * p.stride - 1;
+        const int y0 = yo * p.stride - p.pad_lo, x0 = xo * p.stride - p.pad_lo;
         if (p.up == 0) {
           // no upsampling (all but three convs of a forward): the tap only ADDS a wave-uniform (ky * Win + kx) * lda to the
           // element offset of the row's window origin, and whether a tap falls into the zero padding is one of 9 bits worked

@@ -177,8 +177,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const CoreParams p) {
       int hw = p.Ho * p.Wo;
       int b = m / hw, rem = m - b * hw;
       int yo = rem / p.Wo, xo = rem - yo * p.Wo;
-      ay[i] = yo * p.stride - 1;
-      ax[i] = xo * p.stride - 1;
+      ay[i] = yo * p.stride - p.pad_lo;
+      ax[i] = xo * p.stride - p.pad_lo;
       arow[i] = Ab + (size_t)b * p.Hin * p.Win * p.lda + c * 8;
     } else {
       ay[i] = ax[i] = 0;
@@ -388,8 +388,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel_dma(const CoreParams p) {
       const int hw = p.Ho * p.Wo;
       const int b = m / hw, rem = m - b * hw;
       const int yo = rem / p.Wo, xo = rem - yo * p.Wo;
-      ay[i] = yo * p.stride - 1;
-      ax[i] = xo * p.stride - 1;
+      ay[i] = yo * p.stride - p.pad_lo;
+      ax[i] = xo * p.stride - p.pad_lo;
       arow[i] = Ab + (size_t)b * p.Hin * p.Win * p.lda + c * 8;
     }
     tap = (kt_begin * BK) / p.Cin;
@@ -581,8 +581,8 @@ __global__ __launch_bounds__(256, 1) void gemm_kernel_ring(const CoreParams p) {
       const int hw = p.Ho * p.Wo;
       const int b = m / hw, rem = m - b * hw;
       const int yo = rem / p.Wo, xo = rem - yo * p.Wo;
-      ay[j] = yo * p.stride - 1;
-      ax[j] = xo * p.stride - 1;
+      ay[j] = yo * p.stride - p.pad_lo;
+      ax[j] = xo * p.stride - p.pad_lo;
       asrc[j] = Ab + (size_t)b * p.Hin * p.Win * p.lda + ch;
     }
   }
@@ -1084,7 +1084,8 @@ extern "C" int idf_gemm(const idf_gemm_args* a, void* stream) {
   return rc;
 }
 
-extern "C" int idf_conv3x3(const idf_conv3x3_args* a, void* stream) {
+// the launcher behind idf_conv3x3 (pad_lo = 1) and idf_conv3x3_down (pad_lo = 0); one zero row / column behind the image in both
+static int conv3x3_launch(const idf_conv3x3_args* a, int pad_lo, void* stream) {
   if (!a || !a->x || !a->W || !a->out) return IDF_E_ARG;
   if (a->B <= 0 || a->Cin <= 0 || (a->Cin % BK) != 0 || a->Cout <= 0) return IDF_E_ARG;
   if (a->stride != 1 && a->stride != 2) return IDF_E_ARG;
@@ -1095,10 +1096,10 @@ extern "C" int idf_conv3x3(const idf_conv3x3_args* a, void* stream) {
   if ((a->epi & IDF_EPI_BIAS) && !a->bias) return IDF_E_ARG;
   CoreParams p{};
   const int Hup = a->Hin << a->upsample, Wup = a->Win << a->upsample;
-  p.Ho = (Hup - 1) / a->stride + 1; p.Wo = (Wup - 1) / a->stride + 1;
+  p.Ho = (Hup + pad_lo - 2) / a->stride + 1; p.Wo = (Wup + pad_lo - 2) / a->stride + 1;
   p.W = (const unsigned short*)a->W; p.ldw = 9 * a->Cin; p.strideW = 0; p.N = a->Cout;
   p.A = (const unsigned short*)a->x; p.lda = a->ldx; p.strideA = 0; p.M = a->B * p.Ho * p.Wo; p.K = 9 * a->Cin;
-  p.Hin = a->Hin; p.Win = a->Win; p.Cin = a->Cin; p.stride = a->stride; p.up = a->upsample;
+  p.Hin = a->Hin; p.Win = a->Win; p.Cin = a->Cin; p.stride = a->stride; p.up = a->upsample; p.pad_lo = pad_lo;
   p.out = a->out; p.ldo = a->ldo; p.strideO = 0;
   p.bias = a->bias; p.rowbias = (const unsigned short*)a->rowbias; p.ld_rowbias = a->ld_rowbias;
   p.rows_per_batch = p.Ho * p.Wo;
@@ -1122,4 +1123,11 @@ extern "C" int idf_conv3x3(const idf_conv3x3_args* a, void* stream) {
   if (rc == 0 && a->gn_partial && !gst)
     rc = idf_groupnorm_stats(a->out, a->gn_partial, a->B, p.Ho * p.Wo, a->Cout, p.Ho * p.Wo / 64, a->dtype, stream);
   return rc;
+}
+
+extern "C" int idf_conv3x3(const idf_conv3x3_args* a, void* stream) { return conv3x3_launch(a, 1, stream); }
+
+extern "C" int idf_conv3x3_down(const idf_conv3x3_args* a, void* stream) {
+  if (!a || a->stride != 2 || a->upsample != 0 || a->Hin < 2 || a->Win < 2) return IDF_E_ARG;
+  return conv3x3_launch(a, 0, stream);
 }

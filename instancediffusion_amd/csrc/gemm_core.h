@@ -37,6 +37,9 @@ struct CoreParams {
   // dephase = P start groups per XCD (0 / 1: off), dephase_units = one tile's estimated duration in units of 1024 cycles;
   // epi_vmcnt = 1: the first K-tile behind an epilogue waits with a counted vmcnt (the epilogue's stores drain under it)
   int tile_walk; int dephase; int dephase_units; int epi_vmcnt;
+  // conv gather: zero rows / columns in front of the image (the window origin is yo * stride - pad_lo).  1 = the symmetric
+  // pad 1 of idf_conv3x3; 0 = idf_conv3x3_down (the VAE encoder's Downsample pads right and bottom only).  Wave-uniform.
+  int pad_lo;
 };
 
 constexpr int BK = 64;

@@ -346,6 +346,51 @@ __global__ void pointwise_nchw_kernel(const float* __restrict__ x, const float* 
   }
 }
 
+// Everything of AutoencoderKL.encode behind the encoder's conv_out (autoencoder.py:27-31, distributions.py:24-37) on fp32 NCHW:
+// moments = quant_conv(h) (1x1, [2E][C2]), (mean | logvar) = its channel halves, logvar clamped to [-30, 20],
+// z = (mean + exp(0.5 logvar) * noise) * scale; noise == nullptr: the mode.  A thread owns V consecutive pixels of a sample.
+template <int V>
+__global__ void vae_posterior_kernel(const float* __restrict__ h, const float* __restrict__ w, const float* __restrict__ bias,
+                                     const float* __restrict__ noise, float scale, float* __restrict__ z,
+                                     float* __restrict__ moments, int B, int C2, int E, long long HW) {
+  static_assert(V == 1 || V == 4, "scalar or 16-B accesses");
+  auto ld = [](const float* p, float* v) {
+    if constexpr (V == 4) { const f32x4 t = *reinterpret_cast<const f32x4*>(p); v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; }
+    else v[0] = p[0];
+  };
+  auto st = [](float* p, const float* v) {
+    if constexpr (V == 4) *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
+    else p[0] = v[0];
+  };
+  const long long per = HW / V;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)B * per) return;
+  const long long b = i / per, pix = (i - b * per) * V;
+  float xv[16][V];
+  for (int ci = 0; ci < C2; ++ci) ld(h + (b * C2 + ci) * HW + pix, xv[ci]);
+  for (int e = 0; e < E; ++e) {
+    float mean[V], lv[V], nz[V], out[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) { mean[j] = bias ? bias[e] : 0.f; lv[j] = bias ? bias[E + e] : 0.f; }
+    for (int ci = 0; ci < C2; ++ci) {
+      const float wm = w[e * C2 + ci], wl = w[(E + e) * C2 + ci];
+#pragma unroll
+      for (int j = 0; j < V; ++j) { mean[j] = fmaf(wm, xv[ci][j], mean[j]); lv[j] = fmaf(wl, xv[ci][j], lv[j]); }
+    }
+    if (noise) ld(noise + (b * E + e) * HW + pix, nz);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      lv[j] = fminf(fmaxf(lv[j], -30.f), 20.f);
+      out[j] = (noise ? fmaf(expf(0.5f * lv[j]), nz[j], mean[j]) : mean[j]) * scale;
+    }
+    st(z + (b * E + e) * HW + pix, out);
+    if (moments) {
+      st(moments + (b * 2 * E + e) * HW + pix, mean);
+      st(moments + (b * 2 * E + E + e) * HW + pix, lv);
+    }
+  }
+}
+
 inline dim3 grid1d(long long n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
 }  // namespace
@@ -473,5 +518,15 @@ extern "C" int idf_pointwise_nchw(const float* x, const float* w, const float* b
   if (!x || !w || !out || B <= 0 || Cin <= 0 || Cin > 16 || Cout <= 0 || HW <= 0) return IDF_E_ARG;
   hipLaunchKernelGGL(pointwise_nchw_kernel, grid1d((long long)B * HW), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, B, Cin,
                      Cout, HW, in_scale);
+  return idf_launch_status();
+}
+
+extern "C" int idf_vae_posterior(const float* h, const float* w, const float* bias, const float* noise, float scale, float* z,
+                                 float* moments, int B, int C2, int E, long long HW, void* stream) {
+  if (!h || !w || !z || B <= 0 || C2 <= 0 || C2 > 16 || E <= 0 || 2 * E > 16 || HW <= 0) return IDF_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const bool v4 = (HW % 4) == 0 && aligned16(h) && aligned16(z) && (!noise || aligned16(noise)) && (!moments || aligned16(moments));
+  if (v4) hipLaunchKernelGGL(vae_posterior_kernel<4>, grid1d((long long)B * (HW / 4)), dim3(256), 0, s, h, w, bias, noise, scale, z, moments, B, C2, E, HW);
+  else hipLaunchKernelGGL(vae_posterior_kernel<1>, grid1d((long long)B * HW), dim3(256), 0, s, h, w, bias, noise, scale, z, moments, B, C2, E, HW);
   return idf_launch_status();
 }

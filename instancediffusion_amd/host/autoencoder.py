@@ -3,12 +3,14 @@
 SURVEY.md §8 row f-2: ``AutoencoderKL.decode`` is the step right after the sampling path (reference
 ``inference.py:95``: ``samples_fake = autoencoder.decode(samples_fake)``).  Same constructor, same state-dict keys
 (``encoder.*``, ``decoder.*``, ``quant_conv.*``, ``post_quant_conv.*`` -- 248 tensors for the SD-1.5 KL-f8 config) and
-the same ``decode(z) -> image [B, 3, 8H, 8W]`` contract as the reference; the arithmetic runs in
-``instancediffusion_amd.vae_engine.VAEDecoderEngine`` on an MI355X.  There is no CPU / eager fallback.
+the same ``decode(z) -> image [B, 3, 8H, 8W]`` and ``encode(x) -> z [B, embed_dim, H/8, W/8]`` contracts as the reference; the
+arithmetic runs in ``instancediffusion_amd.vae_engine`` (``VAEDecoderEngine`` / ``VAEEncoderEngine``) on an MI355X.  There is no
+CPU / eager fallback for either direction.
 
-``encode`` is NOT on the inference path (it is used by training and inpainting only, ``trainer.py``) and is not
-built: the encoder's parameters exist here so that the reference checkpoint's ``['autoencoder']`` sub-dict loads with
-``strict=True`` (``utils/checkpoint.py:245``), and ``encode`` raises.
+``encode`` is what everything that starts from pixels calls first (inpainting: the ``x0`` of ``PLMSSampler.sample(mask=, x0=)``;
+latent caching; ``trainer.py:153``): ``moments = quant_conv(Encoder(x))``, ``z = sample(moments) * scale_factor``
+(``autoencoder.py:27-31``), the posterior noise drawn on the CPU from the default generator as the reference does
+(``distributions.py:36``).
 """
 from __future__ import annotations
 
@@ -58,7 +60,7 @@ class Upsample(nn.Module):
 
 
 class Downsample(nn.Module):
-    """model.py:59-79 (parameter container only: the encoder is not on the inference path)."""
+    """model.py:59-79: zero-pad right and bottom, then 3x3 stride 2 without padding; executed as ``idf_conv3x3_down``."""
 
     def __init__(self, in_channels: int, with_conv: bool = True):
         super().__init__()
@@ -83,7 +85,7 @@ def _mid(ch: int) -> nn.Module:
 
 
 class Encoder(nn.Module):
-    """model.py:368-460 -- parameter container (state-dict compatibility); no forward."""
+    """model.py:368-460 -- same module tree / key names; executed by ``VAEEncoderEngine``."""
 
     def __init__(self, *, ch, out_ch, ch_mult=(1, 2, 4, 8), num_res_blocks, attn_resolutions, dropout=0.0,
                  resamp_with_conv=True, in_channels, resolution, z_channels, double_z=True, use_linear_attn=False,
@@ -166,11 +168,14 @@ class AutoencoderKL(nn.Module):
         self.scale_factor = scale_factor
         self.compute_dtype = torch.bfloat16     # 16-bit storage / MFMA input type of the HIP engine (or float16)
         self.max_decode_batch = 4               # images per decoder pass (activations at 512^2 x 128 ch: 67 MB each)
+        self.max_encode_batch = 4               # images per encoder pass (the same activations, in the other direction)
         self._engine = None
+        self._enc_engine = None
 
     def load_state_dict(self, *a, **k):
         r = super().load_state_dict(*a, **k)
         self._engine = None
+        self._enc_engine = None
         return r
 
     @property
@@ -180,10 +185,50 @@ class AutoencoderKL(nn.Module):
             self._engine = VAEDecoderEngine(self, dtype=self.compute_dtype)
         return self._engine
 
-    def encode(self, x):
-        raise NotImplementedError(
-            "AutoencoderKL.encode is outside the sampling path (training / inpainting only, SURVEY.md §8 f-2); "
-            "use the reference encoder")
+    @property
+    def encoder_engine(self):
+        if self._enc_engine is None:
+            from ..vae_engine import VAEEncoderEngine
+            self._enc_engine = VAEEncoderEngine(self, dtype=self.compute_dtype)
+        return self._enc_engine
+
+    @torch.no_grad()
+    def encode(self, x: torch.Tensor, noise=None, return_moments: bool = False):
+        """autoencoder.py:27-31: image x [B, 3, H, W] fp32 in [-1, 1] (any device) -> latent z [B, embed_dim, H/8, W/8] fp32 on the
+        GPU, already multiplied by ``scale_factor``.
+
+        ``noise=None``: the posterior sample with ``torch.randn(mean.shape)`` drawn on the CPU from the default generator -- the
+        reference's own call (distributions.py:36), so ``torch.manual_seed(s); ae.encode(x)`` consumes the same random numbers as
+        the reference.  ``noise=<tensor>``: that noise.  ``noise=False``: the mode (``mean * scale_factor``).
+        ``return_moments=True`` returns ``(z, mean, logvar)``, the moments unscaled and logvar clamped to [-30, 20]."""
+        try:
+            eng = self.encoder_engine
+        except (RuntimeError, OSError) as e:
+            raise NotImplementedError(
+                "AutoencoderKL.encode has no CPU path: it runs on the HIP kernels of libidf_gfx950.so on an MI355X, and that "
+                f"engine could not be created ({e})") from e
+        if x.dim() != 4 or x.shape[1] != self.encoder.in_channels:
+            raise ValueError(f"AutoencoderKL.encode expects [B, {self.encoder.in_channels}, H, W], got {tuple(x.shape)}")
+        B, _, H, W = x.shape
+        eng.check_size(H, W)
+        f, E = eng.down_factor, self.embed_dim
+        if noise is None:
+            noise = torch.randn((B, E, H // f, W // f))
+        elif noise is False:
+            noise = None
+        elif tuple(noise.shape) != (B, E, H // f, W // f):
+            raise ValueError(f"noise must be {(B, E, H // f, W // f)}, got {tuple(noise.shape)}")
+        zs, ms = [], []
+        for i in range(0, B, self.max_encode_batch):
+            j = i + self.max_encode_batch
+            z, m = eng.encode(x[i:j].float(), None if noise is None else noise[i:j].float())
+            zs.append(z)
+            ms.append(m)
+        z = zs[0] if len(zs) == 1 else torch.cat(zs, 0)
+        if not return_moments:
+            return z
+        m = ms[0] if len(ms) == 1 else torch.cat(ms, 0)
+        return z, m[:, :E], m[:, E:]
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor) -> torch.Tensor:

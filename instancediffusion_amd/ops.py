@@ -229,6 +229,34 @@ class HipOps:
         _lib.check(self.lib.idf_conv3x3(C.byref(args), self._stream()), "idf_conv3x3")
         return out
 
+    def conv3x3_down(self, x, w, out, *, bias=None, res=None, gn_partial=None):
+        """The VAE encoder's Downsample (``idf_conv3x3_down``): zero-pad right and bottom only, 3x3 stride 2.
+        x [B,H,W,Cin] view (channel-contiguous), w [Cout, 9*Cin]; out [B,(H-2)//2+1,(W-2)//2+1,Cout] 16-bit."""
+        B, H, W_, Cin = x.shape
+        assert x.stride(-1) == 1 and x.stride(1) == W_ * x.stride(2) and x.stride(0) == H * x.stride(1)
+        Cout = w.shape[0]
+        assert tuple(out.shape) == (B, (H - 2) // 2 + 1, (W_ - 2) // 2 + 1, Cout) and out.stride(-1) == 1
+        assert out.stride(1) == out.shape[2] * out.stride(2) and out.stride(0) == out.shape[1] * out.stride(1)
+        epi = 0
+        if bias is not None:
+            epi |= EPI_BIAS
+        if res is not None:
+            epi |= EPI_RES
+        args = _lib.ConvArgs(
+            x=x.data_ptr(), W=w.data_ptr(), out=out.data_ptr(),
+            bias=None if bias is None else bias.data_ptr(), rowbias=None,
+            res=None if res is None else res.data_ptr(),
+            B=B, Hin=H, Win=W_, Cin=Cin, Cout=Cout, stride=2, upsample=0,
+            ldx=x.stride(2), ldo=out.stride(2), ldr=0 if res is None else res.stride(2),
+            ld_rowbias=0, n_valid=0, epi=epi, dtype=self.dt,
+            ws=self._splitk_ws().data_ptr(), ws_bytes=self.SPLITK_WS_BYTES,
+            gn_partial=None if gn_partial is None else gn_partial.data_ptr())
+        if gn_partial is not None:
+            assert gn_partial.dtype == torch.float32 and gn_partial.is_contiguous() and out.is_contiguous()
+            assert tuple(gn_partial.shape) == self.gn_partial_shape(out.shape[0], out.shape[1] * out.shape[2], Cout)
+        _lib.check(self.lib.idf_conv3x3_down(C.byref(args), self._stream()), "idf_conv3x3_down")
+        return out
+
     def conv_in(self, x_nchw, w, bias, out):
         B, Cin, H, W_ = x_nchw.shape
         assert x_nchw.dtype == torch.float32 and x_nchw.is_contiguous() and out.is_contiguous()
@@ -389,3 +417,20 @@ class HipOps:
         _lib.check(self.lib.idf_pointwise_nchw(_p(x), _p(w), _p(bias), _p(out), B, Cin, Cout, HW, float(in_scale),
                                                self._stream()), "idf_pointwise_nchw")
         return out
+
+    def vae_posterior(self, h, w, bias, noise, scale, z, moments=None):
+        """Everything of ``AutoencoderKL.encode`` behind the encoder's conv_out, fp32 NCHW: h [B,C2,H,W], w [2E,C2], bias [2E] or
+        None, noise [B,E,H,W] or None (the mode); z [B,E,H,W] = (mean + exp(0.5 clamp(logvar)) * noise) * scale; ``moments``
+        [B,2E,H,W] (optional) receives mean | clamped logvar."""
+        B, C2 = h.shape[0], h.shape[1]
+        E2 = w.shape[0]
+        HW = h.numel() // (B * C2)
+        assert E2 % 2 == 0 and tuple(w.shape) == (E2, C2) and tuple(z.shape) == (B, E2 // 2) + tuple(h.shape[2:])
+        assert noise is None or noise.shape == z.shape
+        assert moments is None or tuple(moments.shape) == (B, E2) + tuple(h.shape[2:])
+        assert bias is None or tuple(bias.shape) == (E2,)
+        for t in (h, w, z) + tuple(t for t in (bias, noise, moments) if t is not None):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        _lib.check(self.lib.idf_vae_posterior(_p(h), _p(w), _p(bias), _p(noise), float(scale), _p(z), _p(moments), B, C2, E2 // 2,
+                                              HW, self._stream()), "idf_vae_posterior")
+        return z
