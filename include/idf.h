@@ -209,6 +209,19 @@ int idf_conv3x3(const idf_conv3x3_args* a, void* stream);
  * anything else is IDF_E_ARG before any launch.  Added within ABI 5: a new symbol only, no struct or existing entry point
  * changed, so callers built against the earlier ABI 5 header are unaffected. */
 int idf_conv3x3_down(const idf_conv3x3_args* a, void* stream);
+/* Upsample (openaimodel.py:98,107: F.interpolate(x, scale_factor=2, mode="nearest") then the 3x3 pad-1 conv) with the upsample
+ * folded into the WEIGHTS instead of the gather: output pixel (2y + py, 2x + px) sees only a 2x2 window of the low-resolution image,
+ * so the layer is four 2x2 convs (one per parity phase), 4 Cin multiply-adds per output instead of 9 Cin.
+ *   W is [4][Cout][(ty*2+tx)*Cin + ci], phases in the order (py, px) = (0,0), (0,1), (1,0), (1,1); tap (ty, tx) of phase (py, px) reads
+ *   x[y - 1 + py + ty][x - 1 + px + tx] (zero outside the image) and its weight is the sum of the 3x3 taps that land on that pixel:
+ *   rows  py = 0: {ty 0: w[0], ty 1: w[1] + w[2]},  py = 1: {ty 0: w[0] + w[1], ty 1: w[2]};  columns likewise.
+ *   (Sum the fp32 master weights and round to 16 bit once.)
+ * The idf_conv3x3 argument block describing the layer it replaces: x [B, Hin, Win, Cin], out [B, 2 Hin, 2 Win, Cout] 16-bit NHWC,
+ * stride 1, upsample 1, epi 0 or IDF_EPI_BIAS; rowbias, res, gn_partial NULL, n_valid 0 (else IDF_E_ARG); ws unused.
+ * Runs on the persistent 256 x 320 kernel only (one launch, counted in IDF_STAT_GEMM_BIG_LAUNCHES): Cout % 320 == 0 and a tile
+ * grid that passes its occupancy bar; any other shape returns IDF_E_UNSUPPORTED BEFORE any launch and the caller runs
+ * idf_conv3x3(upsample = 1) with the 3x3 image.  Added within ABI 5 like idf_conv3x3_down: a new symbol only. */
+int idf_conv_up2x_folded(const idf_conv3x3_args* a, void* stream);
 
 /* first conv 4->C directly from the fp32 NCHW latent (openaimodel.py:371, :469-480): out NHWC 16-bit */
 int idf_conv_in(const float* x_nchw, const float* w /*[C][Cin][3][3]*/, const float* bias, void* out,

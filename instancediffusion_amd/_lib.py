@@ -35,6 +35,9 @@ class GemmArgs(C.Structure):
                 ("vt_out", vp), ("ld_vt", ci), ("vt_col0", ci)]
 
 
+E_UNSUPPORTED = -3                       # IDF_E_UNSUPPORTED (include/idf.h)
+
+
 class ConvArgs(C.Structure):
     _fields_ = [("x", vp), ("W", vp), ("out", vp), ("bias", vp), ("rowbias", vp), ("res", vp),
                 ("B", ci), ("Hin", ci), ("Win", ci), ("Cin", ci), ("Cout", ci),
@@ -66,6 +69,7 @@ SYMBOLS = {
     "idf_gemm": (ci, [C.POINTER(GemmArgs), vp]),
     "idf_conv3x3": (ci, [C.POINTER(ConvArgs), vp]),
     "idf_conv3x3_down": (ci, [C.POINTER(ConvArgs), vp]),
+    "idf_conv_up2x_folded": (ci, [C.POINTER(ConvArgs), vp]),
     "idf_mlp_geglu": (ci, [C.POINTER(MlpArgs), vp]),
     "idf_conv_in": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
     "idf_attention": (ci, [C.POINTER(AttnArgs), vp]),

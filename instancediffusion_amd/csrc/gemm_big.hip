@@ -568,6 +568,57 @@ __device__ __forceinline__ void big_epilogue_vt(const CoreParams& p, f32x16 (&ac
   });
 }
 
+// Epilogue of a FOLD tile (nearest-x2 upsample folded into the weights, idf_conv_up2x_folded): row m = (b, y, x) of parity phase
+// (py, px) is pixel (b, 2y + py, 2x + px) of the [B, 2H, 2W, N] output, i.e. output row 4m - 2x + py * 2W + px.  Bias only (these
+// layers feed a ScaleU concat: no GroupNorm partials, no residual, no row bias); 16-bit output, the lane's 16 columns as 2 x 16 B
+// exactly like the plain epilogue -- only the row a lane stores to moves.
+template <int DT, int BM, int BN, int TN>
+__device__ __forceinline__ void big_epilogue_fold(const CoreParams& p, f32x16 (&acc)[TN][TM], int tile, int ph, int tiles_n, int wm,
+                                                  int wn, int l31_in, int hi_in) {
+  constexpr int WN = BN / 2;
+  int l31 = l31_in, hi = hi_in;                             // opaque copies, as in big_epilogue
+  asm volatile("" : "+v"(l31), "+v"(hi));
+  const int m_tile = tile / tiles_n;
+  const int n0 = (tile - m_tile * tiles_n) * BN, m0 = m_tile * BM;
+  const int mw = m0 + wm * WM, nw = n0 + wn * WN;
+  const int ph_row = (ph >> 1) * 2 * p.Wo + (ph & 1);
+  unsigned short* orow[TM];
+#pragma unroll
+  for (int b = 0; b < TM; ++b) {
+    const int m = min(mw + b * 32 + l31, p.M - 1);
+    const int x = m % p.Wo;
+    orow[b] = reinterpret_cast<unsigned short*>(p.out) + (size_t)(4 * m - 2 * x + ph_row) * p.ldo;
+  }
+  static_for<0, TN, 1>([&](auto AI) {
+    constexpr int a = decltype(AI)::value;
+    const int n = nw + a * 32 + 16 * hi;
+    f32x4 bs[4];
+    if (p.epi & IDF_EPI_BIAS) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bs[j] = *reinterpret_cast<const f32x4*>(p.bias + n + 4 * j);
+    }
+#pragma unroll
+    for (int b = 0; b < TM; ++b) {
+      float v[16];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const auto s02 = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[a][b][e]), __float_as_uint(acc[a][b][8 + e]), false, false);
+        const auto s13 = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[a][b][4 + e]), __float_as_uint(acc[a][b][12 + e]), false, false);
+        v[e] = __uint_as_float(s02[0]); v[4 + e] = __uint_as_float(s02[1]);
+        v[8 + e] = __uint_as_float(s13[0]); v[12 + e] = __uint_as_float(s13[1]);
+      }
+      if (p.epi & IDF_EPI_BIAS) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] += bs[j >> 2][j & 3];
+      }
+      if (mw + b * 32 + l31 < p.M) {
+        *reinterpret_cast<u32x4*>(orow[b] + n) = pack8<DT>(v);
+        *reinterpret_cast<u32x4*>(orow[b] + n + 8) = pack8<DT>(v + 8);
+      }
+    }
+  });
+}
+
 // Optional per-segment cycle trace (tools/ubench/big_trace.hip builds this file with -DIDF_BIG_TRACE; the library build has
 // none of it): s_memtime deltas summed per segment by waves 0 (early filler) and 4 (late filler) of the first and of a
 // middle workgroup.  Segments: 0 vmcnt wait, 1 barrier, 2 early K-tile enqueue, 3 fragment reads + MFMA issue (+ late
@@ -589,7 +640,7 @@ __device__ unsigned long long idf_big_trace_buf[4][8];
 // Geometry: BM x BN output tile, (BM/64) x 2 waves (wave tile 64 x BN/2), K-tile BKT, NSTG-stage LDS ring.
 //   <256, {320,256}, 64, 2>: ONE 8-wave workgroup per CU (2 x 72 KB stages); <256, 128, 64, 3>: 3 x 48 KB stages.
 template <int DT, int BM, int BN, int BKT, int NSTG, bool CONV, bool SPLIT, bool LNS = false, bool VT = false, bool STATS = false,
-          bool GLU = false, bool GST = false>
+          bool GLU = false, bool GST = false, bool FOLD = false>
 __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CoreParams p, const int tiles_total) {
   constexpr int WN = BN / 2, TN = WN / 32;
   constexpr int NW = NWAVES;                               // waves per workgroup: (BM / WM) x 2
@@ -647,13 +698,18 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
   auto setup_loader = [&](int item) {
     int tile, slice;
     item_map(item, tile, slice, l_nk);
+    // FOLD: the output parity phase (py, px) = (ph >> 1, ph & 1) is the slowest part of the tile index; a phase has its own
+    // weight image (N rows each) and its own 2x2 window origin
+    [[maybe_unused]] int ph = 0;
+    if constexpr (FOLD) { ph = tile / p.fold_tiles; tile -= ph * p.fold_tiles; }
     const int m_tile = tile / tiles_n;
     const int n0 = (tile - m_tile * tiles_n) * BN, m0 = m_tile * BM;
     l_k0 = slice * nk;
 #pragma unroll
     for (int j = 0; j < W_INST; ++j) {
       const int row = RPI * (wave + NW * j) + dr;
-      woff[j] = (unsigned)(n0 + row) * (unsigned)p.ldw + (unsigned)((dc ^ swz(row)) * 8);
+      if constexpr (FOLD) woff[j] = (unsigned)(ph * p.N + n0 + row) * (unsigned)p.ldw + (unsigned)((dc ^ swz(row)) * 8);
+      else woff[j] = (unsigned)(n0 + row) * (unsigned)p.ldw + (unsigned)((dc ^ swz(row)) * 8);
     }
 #pragma unroll
     for (int j = 0; j < A_INST; ++j) {
@@ -664,6 +720,20 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
         const int hw = p.Ho * p.Wo;
         const int b = m / hw, rem = m - b * hw;
         const int yo = rem / p.Wo, xo = rem - yo * p.Wo;
+        if constexpr (FOLD) {
+          // 2x2 window on the low-resolution image: output row 2 yo + py reads source rows yo - 1 + py and yo + py (columns
+          // likewise), and the zero padding of the upsampled image is the zero padding of this one -- a 4-bit mask
+          const int y0 = yo - 1 + (ph >> 1), x0 = xo - 1 + (ph & 1);
+          int mask = 0;
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const int yi = y0 + (t >> 1), xi = x0 + (t & 1);
+            mask |= ((yi >= 0) & (yi < p.Hin) & (xi >= 0) & (xi < p.Win)) << t;
+          }
+          ayx[j] = mask;
+          aoff[j] = (unsigned)b * (unsigned)(p.Hin * p.Win) * (unsigned)p.lda + (unsigned)((y0 * p.Win + x0) * p.lda) + sw;
+          continue;
+        }
         const int y0 = yo * p.stride - p.pad_lo, x0 = xo * p.stride - p.pad_lo;
         if (p.up == 0) {
           // no upsampling (all but three convs of a forward): the tap only ADDS a wave-uniform (ky * Win + kx) * lda to the
@@ -701,7 +771,12 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
     } else {
       constexpr int j = i - W_INST;
       const unsigned dst = lds_addr(Al + RPI * (wave + NW * j) * RS);
-      if (CONV && p.up == 0) {
+      if constexpr (FOLD) {
+        const unsigned tapoff = (unsigned)(((tap >> 1) * p.Win + (tap & 1)) * p.lda + ci0);   // wave-uniform
+        const bool ok = (ayx[j] >> tap) & 1;
+        const unsigned short* src = ok ? p.A + (aoff[j] + tapoff) : idf_zero_page + dc * 8;
+        dma16_v(src, dst);
+      } else if (CONV && p.up == 0) {
         const int ky = tap / 3, kx = tap - ky * 3;
         const unsigned tapoff = (unsigned)((ky * p.Win + kx) * p.lda + ci0);          // wave-uniform
         const bool ok = (ayx[j] >> tap) & 1;
@@ -857,6 +932,8 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
     constexpr bool SPL = decltype(SPLT)::value;               // this item is one K-slice of a tail tile
     int tile, slice, nki;
     item_map(seq, tile, slice, nki);
+    [[maybe_unused]] int ph = 0;
+    if constexpr (FOLD) { ph = tile / p.fold_tiles; tile -= ph * p.fold_tiles; }
     f32x16 acc[TN][TM];
     float lsx[TM], lsq[TM];                               // LNS: per-lane partial sum / sum of squares of its A rows
 #pragma unroll
@@ -949,6 +1026,8 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
       } else {
         big_epilogue_vt<DT, BM, BN, TN>(p, acc, seq, tiles_n, wm, wn, l31, hi, p.ln_stats, 0);
       }
+    } else if constexpr (FOLD) {
+      big_epilogue_fold<DT, BM, BN, TN>(p, acc, tile, ph, tiles_n, wm, wn, l31, hi);
     } else {
       big_epilogue<DT, BM, BN, TN, SPL, LNS, STATS, GLU, GST>(p, acc, tile, slice, tiles_n, wm, wn, l31, hi, gate, stg, lnm, lnr);
     }
@@ -1015,16 +1094,16 @@ BigSched& big_sched() {
 }
 
 template <int DT, int BN, int NSTG, bool CONV, bool SPLIT = false, bool LNS = false, bool VT = false, bool STATS = false, bool GLU = false,
-          bool GST = false>
+          bool GST = false, bool FOLD = false>
 int launch_big_cfg(const CoreParams& p, hipStream_t s, int splitk = 1) {
   constexpr int BM = 256, BKT = 64;
-  if constexpr (!SPLIT && !LNS && !VT && !STATS && !GLU && !GST && NSTG == 2) {
+  if constexpr (!SPLIT && !LNS && !VT && !STATS && !GLU && !GST && !FOLD && NSTG == 2) {
     if (splitk > 1) return launch_big_cfg<DT, BN, NSTG, CONV, true>(p, s, splitk);
   }
   if constexpr (!SPLIT && !LNS && !CONV && !STATS && !GST && NSTG == 2) {
     if ((p.epi & IDF_EPI_LN_ROW) && !p.ln_stats) return launch_big_cfg<DT, BN, NSTG, CONV, false, true, VT, false, GLU>(p, s, 1);
   }
-  void (*kern)(const CoreParams, const int) = gemm_kernel_big<DT, BM, BN, BKT, NSTG, CONV, SPLIT, LNS, VT, STATS, GLU, GST>;
+  void (*kern)(const CoreParams, const int) = gemm_kernel_big<DT, BM, BN, BKT, NSTG, CONV, SPLIT, LNS, VT, STATS, GLU, GST, FOLD>;
   constexpr int smem = NSTG * (BM + BN) * BKT * 2 + NWAVES * 2048;      // ring + one 2-KB slot per wave (160 KB at BN = 320)
   static std::atomic<unsigned long long> attr_done{0};
   if (const int e = idf_lds_optin(reinterpret_cast<const void*>(kern), smem, attr_done)) return e;
@@ -1033,7 +1112,8 @@ int launch_big_cfg(const CoreParams& p, hipStream_t s, int splitk = 1) {
   const int tiles_all = (p.N / BN) * ((p.M + BM - 1) / BM);
   if (!SPLIT) { q.full_items = tiles_all; q.tail_m0 = 0; q.tail_rows = p.M; }
   // (SPLIT: full_items / tail_m0 / tail_rows were set by the dispatcher; uniform split-K = 0 / 0 / M)
-  const int tiles = q.full_items + (tiles_all - q.full_items) * splitk;   // work items
+  int tiles = q.full_items + (tiles_all - q.full_items) * splitk;   // work items
+  if constexpr (FOLD) { q.fold_tiles = tiles_all; tiles = 4 * tiles_all; }   // four parity phases, phase-major
   const int slots = num_cu();
   const int grid = tiles < slots ? tiles : slots;
   {                                                       // schedule knobs (all bit-identical; see the kernel)
@@ -1190,5 +1270,28 @@ int idf_launch_big(const CoreParams& p, int dtype, bool conv, bool force, hipStr
   if (dtype == IDF_BF16) { IDF_BIG_DISPATCH(IDF_BF16) }
   if (dtype == IDF_F16) { IDF_BIG_DISPATCH(IDF_F16) }
 #undef IDF_BIG_DISPATCH
+  return IDF_E_UNSUPPORTED;
+}
+
+// Shape gate of the folded-upsample launch: whole 320-wide tiles, unsplit, whole K-tiles per tap; the same occupancy bar as the
+// automatic rule above (counted over the 4 x tiles work items of the one launch).
+int idf_launch_big_fold(const CoreParams& p, int dtype, bool force, hipStream_t s) {
+  if (p.Cin <= 0 || (p.Cin % BK) != 0 || p.K != 4 * p.Cin || p.ldw != p.K) return IDF_BIG_UNSUPPORTED;
+  if ((p.N % 320) != 0 || p.n_valid != p.N || (p.epi & ~IDF_EPI_BIAS)) return IDF_BIG_UNSUPPORTED;
+  if ((p.lda % 8) || (p.ldo % 8) || !aligned16(p.A) || !aligned16(p.W) || !aligned16(p.out)) return IDF_BIG_UNSUPPORTED;
+  if ((p.epi & IDF_EPI_BIAS) && !aligned16(p.bias)) return IDF_BIG_UNSUPPORTED;
+  if (p.Ho != p.Hin || p.Wo != p.Win || p.M <= 0 || (p.M % (p.Hin * p.Win)) != 0) return IDF_BIG_UNSUPPORTED;
+  const long long slots = (long long)num_cu();
+  const long long items = 4ll * (p.N / 320) * ((p.M + 255) / 256);
+  if (!force) {
+    const long long rounds = (items + slots - 1) / slots;
+    if ((double)items / (double)(rounds * slots) * 100.0 < (double)idf_big_min_eff_pct(-1)) return IDF_BIG_UNSUPPORTED;
+  }
+  // the loader uses 32-bit element offsets (activation rows, the four weight images); the tile index is an int
+  if ((unsigned long long)p.M * (unsigned long long)p.lda >= (1ull << 31) || 4ull * p.N * p.ldw >= (1ull << 31) ||
+      items >= (1ll << 30) || (unsigned long long)p.M * 4ull >= (1ull << 31)) return IDF_BIG_UNSUPPORTED;
+  ++idf_stat_big_launches;
+  if (dtype == IDF_BF16) return launch_big_cfg<IDF_BF16, 320, 2, true, false, false, false, false, false, false, true>(p, s);
+  if (dtype == IDF_F16) return launch_big_cfg<IDF_F16, 320, 2, true, false, false, false, false, false, false, true>(p, s);
   return IDF_E_UNSUPPORTED;
 }

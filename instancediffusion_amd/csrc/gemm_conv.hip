@@ -1131,3 +1131,26 @@ extern "C" int idf_conv3x3_down(const idf_conv3x3_args* a, void* stream) {
   if (!a || a->stride != 2 || a->upsample != 0 || a->Hin < 2 || a->Win < 2) return IDF_E_ARG;
   return conv3x3_launch(a, 0, stream);
 }
+
+// nearest-x2 upsample + 3x3 conv, the upsample folded into the weights: four 2x2 convs on the low-resolution image, one per output
+// parity, as ONE launch of the persistent kernel (gemm_big.hip, FOLD).  No other kernel family carries the folded form: a shape
+// the persistent kernel does not take is IDF_E_UNSUPPORTED before any launch, and the caller runs idf_conv3x3(upsample = 1).
+extern "C" int idf_conv_up2x_folded(const idf_conv3x3_args* a, void* stream) {
+  if (!a || !a->x || !a->W || !a->out) return IDF_E_ARG;
+  if (a->B <= 0 || a->Hin <= 0 || a->Win <= 0 || a->Cin <= 0 || (a->Cin % BK) != 0 || a->Cout <= 0) return IDF_E_ARG;
+  if (a->stride != 1 || a->upsample != 1) return IDF_E_ARG;
+  if ((a->epi & ~IDF_EPI_BIAS) || a->rowbias || a->res || a->gn_partial || a->n_valid) return IDF_E_ARG;
+  if ((a->epi & IDF_EPI_BIAS) && !a->bias) return IDF_E_ARG;
+  if ((a->ldx % 8) || (a->ldo % 8) || !aligned16(a->x) || !aligned16(a->W) || !aligned16(a->out)) return IDF_E_ALIGN;
+  if (a->dtype != IDF_BF16 && a->dtype != IDF_F16) return IDF_E_UNSUPPORTED;
+  const int big = gemm_big_mode();
+  if (big == 0) return IDF_E_UNSUPPORTED;
+  CoreParams p{};
+  p.W = (const unsigned short*)a->W; p.ldw = 4 * a->Cin; p.N = a->Cout; p.n_valid = a->Cout;
+  p.A = (const unsigned short*)a->x; p.lda = a->ldx; p.K = 4 * a->Cin;
+  p.Hin = a->Hin; p.Win = a->Win; p.Cin = a->Cin; p.Ho = a->Hin; p.Wo = a->Win; p.stride = 1; p.up = 0; p.pad_lo = 1;
+  p.M = a->B * a->Hin * a->Win;                           // rows of ONE phase: the low-resolution pixels
+  p.out = a->out; p.ldo = a->ldo; p.bias = a->bias; p.epi = a->epi; p.rows_per_batch = a->Hin * a->Win;
+  const int rc = idf_launch_big_fold(p, a->dtype, big == 2, (hipStream_t)stream);
+  return rc == IDF_BIG_UNSUPPORTED ? IDF_E_UNSUPPORTED : rc;
+}

@@ -40,6 +40,9 @@ struct CoreParams {
   // conv gather: zero rows / columns in front of the image (the window origin is yo * stride - pad_lo).  1 = the symmetric
   // pad 1 of idf_conv3x3; 0 = idf_conv3x3_down (the VAE encoder's Downsample pads right and bottom only).  Wave-uniform.
   int pad_lo;
+  // folded nearest-x2 upsample (gemm_kernel_big<.., FOLD>, idf_conv_up2x_folded): tiles of ONE output parity phase; work item
+  // `tile` belongs to phase tile / fold_tiles.  M, Ho, Wo describe the low-resolution image (one phase), W holds four images.
+  int fold_tiles;
 };
 
 constexpr int BK = 64;
@@ -144,6 +147,9 @@ extern std::atomic<long long> idf_stat_big_launches;     // process-global launc
 // *gst_out (optional): 1 when the kernel left the GroupNorm partials of its output in p.gn_partial (see CoreParams).
 int idf_launch_big(const idfcore::CoreParams& p, int dtype, bool conv, bool force, hipStream_t s, int* splitk_out,
                    int* parts_out = nullptr, int* tail_m0_out = nullptr, int* gst_out = nullptr);
+// nearest-x2 upsample + 3x3 conv as four 2x2 phase convs in one persistent launch (see idf_conv_up2x_folded, include/idf.h);
+// IDF_BIG_UNSUPPORTED = the shape does not qualify (nothing launched).  `force` skips the occupancy bar as in idf_launch_big.
+int idf_launch_big_fold(const idfcore::CoreParams& p, int dtype, bool force, hipStream_t s);
 int idf_launch_qkv320w(const idfcore::CoreParams& p, int dtype, hipStream_t s);   // qkv_fused.hip; IDF_BIG_UNSUPPORTED = not its shape
 int idf_launch_geglu640w(const idfcore::CoreParams& p, int dtype, hipStream_t s);   // geglu_fused.hip; IDF_BIG_UNSUPPORTED = not its shape
 int idf_gegluw_set_mode(int v);                         // 0 = never, 1 = when the shape qualifies; returns the previous mode

@@ -73,6 +73,13 @@ GN_EPI = os.environ.get("IDF_GN_EPI", "1")
 if GN_EPI not in ("0", "1"):
     raise ValueError(f"IDF_GN_EPI={GN_EPI}: must be 0 or 1")
 GN_EPI = GN_EPI == "1"
+# The three Upsample layers (nearest x2, then a 3x3 conv) run as four 2x2 phase convs on the low-resolution image, the upsample
+# folded into the weights at pack time (pack_conv_up2x, idf_conv_up2x_folded): 4 Cin multiply-adds per output pixel instead of 9 Cin.
+# IDF_UP_FOLD=0: the 3x3 conv with the upsample in its gather (idf_conv3x3 upsample=1), as before.
+UP_FOLD = os.environ.get("IDF_UP_FOLD", "1")
+if UP_FOLD not in ("0", "1"):
+    raise ValueError(f"IDF_UP_FOLD={UP_FOLD}: must be 0 or 1")
+UP_FOLD = UP_FOLD == "1"
 DEBUG_PAIRED = os.environ.get("IDF_DEBUG_PAIRED", "0") == "1"     # verify the paired=True guarantee on EVERY forward_cond call
 
 
@@ -93,6 +100,27 @@ def pack_conv3x3(w: torch.Tensor) -> torch.Tensor:
     """[Cout, Cin, 3, 3] -> [Cout, (ky*3+kx)*Cin + ci]  (K order of the implicit-GEMM gather)."""
     co, ci = w.shape[0], w.shape[1]
     return w.permute(0, 2, 3, 1).reshape(co, 9 * ci).contiguous()
+
+
+def pack_conv_up2x(w: torch.Tensor) -> torch.Tensor:
+    """Nearest-x2 upsample folded into a 3x3 pad-1 conv: fp32 [Cout, Cin, 3, 3] -> fp32 [4, Cout, (ty*2+tx)*Cin + ci], one 2x2 conv on
+    the LOW-resolution image per output parity phase, phases in the order (py, px) = (0,0), (0,1), (1,0), (1,1).  Output row 2y + py
+    reads source rows y - 1 + py + ty; the 3x3 rows that land on one source row are summed: py = 0: {ty 0: w[0], ty 1: w[1] + w[2]},
+    py = 1: {ty 0: w[0] + w[1], ty 1: w[2]}; columns likewise.  The zero padding of the upsampled image is the zero padding of the
+    low-resolution one, so the identity is exact.  Sum in fp32 (the master weights); the caller rounds to 16 bit ONCE."""
+    assert w.dim() == 4 and tuple(w.shape[2:]) == (3, 3) and w.dtype == torch.float32
+    co, ci = w.shape[0], w.shape[1]
+    rows = ((w[:, :, 0], w[:, :, 1] + w[:, :, 2]), (w[:, :, 0] + w[:, :, 1], w[:, :, 2]))        # [py][ty] -> [Cout, Cin, 3 (kx)]
+    out = w.new_empty(4, co, 4 * ci)
+    for py in range(2):
+        for px in range(2):
+            taps = []
+            for ty in range(2):
+                r = rows[py][ty]
+                cols = (r[:, :, 0], r[:, :, 1] + r[:, :, 2]) if px == 0 else (r[:, :, 0] + r[:, :, 1], r[:, :, 2])
+                taps += [cols[0], cols[1]]                     # (ty, tx = 0), (ty, tx = 1): [Cout, Cin] each
+            out[py * 2 + px] = torch.stack(taps, dim=1).reshape(co, 4 * ci)
+    return out
 
 
 class _Lin:
@@ -206,6 +234,18 @@ class UNetEngine:
     def _conv(self, m) -> _Lin:
         return _Lin(self._w16(pack_conv3x3(m.weight.detach().float())), self._f32(m.bias))
 
+    def _pack_up(self, m) -> dict:
+        """Upsample conv: the four folded 2x2 phase images (pack_conv_up2x) when the folded path is active, and then NOT the 3x3
+        image -- ``_up_conv3`` packs that one on demand, for a forward whose shape the folded launch does not take."""
+        if UP_FOLD and hasattr(self.ops, "conv_up2x"):
+            return dict(kind="up", conv=None, fold=self._w16(pack_conv_up2x(m.weight.detach().float())), b=self._f32(m.bias), mod=m)
+        return dict(kind="up", conv=self._conv(m), fold=None)
+
+    def _up_conv3(self, p) -> _Lin:
+        if p["conv"] is None:
+            p["conv"] = self._conv(p["mod"])
+        return p["conv"]
+
     # LayerNorm -> Linear pairs are stored FOLDED (include/idf.h IDF_EPI_LN_ROW / LN_COL): the weight carries gamma,
     #   LN(x) W^T = rstd * (x (gamma*W)^T - mu * c) + d,   c = row sums of the 16-bit (gamma*W),   d = W beta (+ bias),
     # so the forward never materialises LN(x): a GEMM reads the raw residual stream and its epilogue applies (mu, rstd).
@@ -293,7 +333,7 @@ class UNetEngine:
             elif isinstance(layer, Downsample):
                 out.append(dict(kind="down", conv=self._conv(layer.op)))
             elif isinstance(layer, Upsample):
-                out.append(dict(kind="up", conv=self._conv(layer.conv)))
+                out.append(self._pack_up(layer.conv))
             else:                                             # first conv
                 out.append(dict(kind="conv_in", w=self._f32(layer.weight), b=self._f32(layer.bias)))
         return out
@@ -733,8 +773,11 @@ class UNetEngine:
                 h = self.ops.conv3x3(h, p["conv"].w, self.buf(out_role, (B, Ho, Wo, C)), bias=p["conv"].b, stride=2, gn_partial=gnp)
             elif k == "up":
                 B, H, W, C = h.shape
-                h = self.ops.conv3x3(h, p["conv"].w, self.buf(out_role + ".up", (B, 2 * H, 2 * W, C)),
-                                     bias=p["conv"].b, upsample=1)
+                up = self.buf(out_role + ".up", (B, 2 * H, 2 * W, C))
+                if p["fold"] is None or not self.ops.conv_up2x(h, p["fold"], up, bias=p["b"]):
+                    conv = self._up_conv3(p)                    # knob off, or a shape the folded launch does not take
+                    self.ops.conv3x3(h, conv.w, up, bias=conv.b, upsample=1)
+                h = up
                 gnp = None                                      # feeds the ScaleU concat, not a GroupNorm
         return h, gnp
 

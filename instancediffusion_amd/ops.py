@@ -257,6 +257,28 @@ class HipOps:
         _lib.check(self.lib.idf_conv3x3_down(C.byref(args), self._stream()), "idf_conv3x3_down")
         return out
 
+    def conv_up2x(self, x, wf, out, *, bias=None) -> bool:
+        """Nearest-x2 upsample + 3x3 conv with the upsample folded into the weights (``idf_conv_up2x_folded``): x [B,H,W,Cin] view
+        (channel-contiguous), wf [4, Cout, 4*Cin] from ``engine.pack_conv_up2x``; out [B,2H,2W,Cout] 16-bit.  Returns False --
+        nothing launched, ``out`` untouched -- when the native path does not take the shape; the caller then runs
+        ``conv3x3(.., upsample=1)`` with the 3x3 image."""
+        B, H, W_, Cin = x.shape
+        assert x.stride(-1) == 1 and x.stride(1) == W_ * x.stride(2) and x.stride(0) == H * x.stride(1)
+        Cout = wf.shape[1]
+        assert tuple(wf.shape) == (4, Cout, 4 * Cin) and wf.is_contiguous() and wf.dtype == self.dtype
+        assert tuple(out.shape) == (B, 2 * H, 2 * W_, Cout) and out.stride(-1) == 1 and out.dtype == self.dtype
+        assert out.stride(1) == out.shape[2] * out.stride(2) and out.stride(0) == out.shape[1] * out.stride(1)
+        args = _lib.ConvArgs(
+            x=x.data_ptr(), W=wf.data_ptr(), out=out.data_ptr(), bias=None if bias is None else bias.data_ptr(),
+            rowbias=None, res=None, B=B, Hin=H, Win=W_, Cin=Cin, Cout=Cout, stride=1, upsample=1,
+            ldx=x.stride(2), ldo=out.stride(2), ldr=0, ld_rowbias=0, n_valid=0, epi=0 if bias is None else EPI_BIAS,
+            dtype=self.dt, ws=None, ws_bytes=0, gn_partial=None)
+        rc = self.lib.idf_conv_up2x_folded(C.byref(args), self._stream())
+        if rc == _lib.E_UNSUPPORTED:
+            return False
+        _lib.check(rc, "idf_conv_up2x_folded")
+        return True
+
     def conv_in(self, x_nchw, w, bias, out):
         B, Cin, H, W_ = x_nchw.shape
         assert x_nchw.dtype == torch.float32 and x_nchw.is_contiguous() and out.is_contiguous()

@@ -35,7 +35,7 @@ torch.cuda.synchronize()
 class ShapeTimer(bench.OpTimer):
     def __getattr__(self, name):
         fn = getattr(self.ops, name)
-        if name not in ("gemm", "conv3x3", "attention", "groupnorm", "layernorm", "scaleu_concat", "row_stats", "mlp_geglu", "conv_in"):
+        if name not in ("gemm", "conv3x3", "attention", "groupnorm", "layernorm", "scaleu_concat", "row_stats", "mlp_geglu", "conv_in", "conv_up2x"):
             return fn
 
         def timed(*a, **k):
@@ -50,6 +50,13 @@ class ShapeTimer(bench.OpTimer):
             elif name == "conv3x3":
                 xx, w, out = a[0], a[1], a[2]
                 key = f"conv {tuple(xx.shape)}->{w.shape[0]} s{k.get('stride', 1)} u{k.get('upsample', 0)}"
+            elif name == "conv_up2x":                          # (x, folded weights [4, Cout, 4 Cin], out) -> False: not taken
+                if not r:
+                    return r
+                xx, wf, out = a[0], a[1], a[2]
+                key = f"conv {tuple(xx.shape)}->{wf.shape[1]} s1 u1 folded"
+                self.records.append((key, 2.0 * (out.numel() // out.shape[-1]) * wf.shape[1] * wf.shape[2], s, e))
+                return r
             elif name == "attention":
                 q = a[0]
                 key = f"attn Nq{q.shape[1]} C{q.shape[2]} n0={a[3]} n1={k.get('n1', 0)}"
