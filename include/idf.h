@@ -49,7 +49,12 @@ enum {
   /* modifier of IDF_EPI_GEGLU: the weight rows are interleaved [16 value | 16 gate] per 32 instead of [32 | 32] per 64.  Value
    * and gate of an output then sit in ONE 32-wide MFMA fragment (registers q and q + 2 of a lane), so the wave tile no longer
    * needs an even number of fragments and the GEGLU GEMMs run on the 320-wide persistent tiles (N % 320 == 0). */
-  IDF_EPI_GEGLU_P32 = 2048
+  IDF_EPI_GEGLU_P32 = 2048,
+  /* idf_gemm only: out = y * sigmoid(1.702 y), y = acc + bias -- the "quick_gelu" of the CLIP text transformer's MLP
+   * (ldm/modules/encoders/modules.py:144-172 -> CLIPTextModel).  Composes with BIAS and LN_ROW (and RES / OUT_F32 like the other
+   * activations); with SILU, GELU or GEGLU it is IDF_E_ARG.  Every idf_gemm kernel family implements it (the persistent kernel, the
+   * small-tile and latency kernels and the split-K reducer); the fused q | k | v form (vt_out) and the convs reject it. */
+  IDF_EPI_QUICKGELU = 4096
 };
 
 int idf_abi_version(void);
@@ -337,6 +342,20 @@ int idf_pointwise_nchw(const float* x, const float* w /*[Cout][Cin]*/, const flo
  * Added within ABI 5 like idf_conv3x3_down: a new symbol only. */
 int idf_vae_posterior(const float* h, const float* w /*[2E][C2]*/, const float* bias, const float* noise, float scale, float* z,
                       float* moments, int B, int C2, int E, long long HW, void* stream);
+
+/* ---- CLIP text transformer (ldm/modules/encoders/modules.py:144-172: FrozenCLIPEmbedder.forward -> CLIPTextModel) ---------------
+ * Its other layers are idf_gemm (LayerNorm folded in with self-computed statistics, BIAS / RES / IDF_EPI_QUICKGELU epilogues) and
+ * idf_layernorm calls.  Both entry points were added within ABI 5: new symbols only.
+ * idf_attention_causal: qkv = the 16-bit row-major output of the fused projection, rows b*T + t, columns [q | k | v], each block H*d
+ * wide, ld >= 3*H*d;  out[b*T + t][h*d + :] = softmax_{j <= t}(scale * q_t . k_j) . v_j  (ldo >= H*d).  One workgroup per (b, h) with
+ * K and V^T of the head resident in LDS, both products on 16x16x32 MFMA, fp32 online softmax, P rounded to the 16-bit type before
+ * P.V; rows <= p do not depend on anything at positions > p bit for bit.  Supported: d == 64, 1 <= T <= 128; anything else is
+ * IDF_E_UNSUPPORTED, a row start that is not 16-B aligned (ld % 8, ldo % 8, the pointers) IDF_E_ALIGN, before any launch.
+ * idf_clip_embed: out[b*T + t][0:C] = tok_emb[ids[b][t]][0:C] + pos_emb[t][0:C] (fp32 sum, one rounding); ids int32 [B][T], tok_emb
+ * 16-bit [vocab][C], pos_emb 16-bit [>= T][C], both contiguous; an id outside [0, vocab) is clamped into it.  C % 8 == 0. */
+int idf_attention_causal(const void* qkv, int ld, void* out, int ldo, int B, int T, int H, int d, float scale, int dtype, void* stream);
+int idf_clip_embed(const int* ids, const void* tok_emb, const void* pos_emb, void* out, int ldo, int B, int T, int C, int vocab,
+                   int dtype, void* stream);
 
 /* ---- layout helpers ---------------------------------------------------------------------------------------*/
 int idf_cast_f32_to_16(const float* x, void* out, long long n, int dtype, void* stream);

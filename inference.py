@@ -105,6 +105,8 @@ def main():
     ap.add_argument("--test_config", type=str, default="configs/test_mask.yaml")
     ap.add_argument("--device", type=str, default="cuda")
     ap.add_argument("--text_encoder", choices=["synthetic", "clip"], default=None)
+    ap.add_argument("--clip_backend", choices=["hf", "hip"], default="hf",
+                    help="CLIP text transformer on Hugging Face transformers (fp32 eager) or on the HIP kernels (--dtype storage)")
     ap.add_argument("--synthetic_weights", action="store_true")
     ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16")
     ap.add_argument("--steps", type=int, default=50)
@@ -141,6 +143,9 @@ def main():
         raise SystemExit("give --ckpt instancediffusion_sd15.pth, or --synthetic_weights for a dry run")
     model.compute_dtype = dtype
     autoencoder.compute_dtype = dtype
+    if clip_text is not None:                  # prompt, negative prompt and phrase encodes all go through this one object
+        clip_text.backend = args.clip_backend
+        clip_text.compute_dtype = dtype
     if args.use_masked_att:
         model.efficient_attention = False      # the reference builds the mask only on its non-efficient path (:189)
         model.invalidate_engine()

@@ -80,6 +80,8 @@ template <int DT> __device__ __forceinline__ u32x4 pack8(const float* f) {
 }
 
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
+// QuickGELU of the CLIP text transformer (transformers' "quick_gelu"): x * sigmoid(1.702 x); the constant carries -log2(e)
+__device__ __forceinline__ float quick_gelu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.4554669595930156f * x)); }
 // erf-GELU (F.gelu default, attention.py:43) as x * sigmoid(p(x)) with p the odd degree-5 minimax fit of logit(Phi(x)):
 //   |gelu_erf_f(x) - x Phi(x)| <= 2.6e-5 for every x (fit on [-8, 8], tools/fit_gelu.py; outside, Phi is 0 / 1 to 1e-15 and
 //   the argument is clamped), i.e. ~1 % of the 2^-9 relative rounding of a 16-bit result of magnitude 1.

@@ -134,7 +134,8 @@ __device__ __forceinline__ void gst_scatter_step(float* t, int l31) {
     t[i] = keep + __shfl_xor(send, H, 64);
   }
 }
-template <int DT, int BM, int BN, int TN, bool SPLIT, bool LNS = false, bool STATS = false, bool GLU = false, bool GST = false>
+template <int DT, int BM, int BN, int TN, bool SPLIT, bool LNS = false, bool STATS = false, bool GLU = false, bool GST = false,
+          bool QG = true /* IDF_EPI_QUICKGELU compiled in: the dense GEMMs; no conv carries the flag */>
 __device__ __forceinline__ void big_epilogue(const CoreParams& p, f32x16 (&acc)[TN][TM], int seq, int slice, int tiles_n, int wm,
                                              int wn, int l31_in, int hi_in, float gate, char* stg_in, const float* lnm = nullptr,
                                              const float* lnr = nullptr) {
@@ -384,6 +385,10 @@ __device__ __forceinline__ void big_epilogue(const CoreParams& p, f32x16 (&acc)[
         if (epi & IDF_EPI_GELU) {
 #pragma unroll
           for (int j = 0; j < 16; ++j) v[j] = gelu_erf_f(v[j]);
+        }
+        if constexpr (QG) if (epi & IDF_EPI_QUICKGELU) {
+#pragma unroll
+          for (int j = 0; j < 16; ++j) v[j] = quick_gelu_f(v[j]);
         }
         if (epi & IDF_EPI_RES) {
           const float gm = (epi & IDF_EPI_GATE) ? gate : 1.0f;
@@ -1029,7 +1034,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
     } else if constexpr (FOLD) {
       big_epilogue_fold<DT, BM, BN, TN>(p, acc, tile, ph, tiles_n, wm, wn, l31, hi);
     } else {
-      big_epilogue<DT, BM, BN, TN, SPL, LNS, STATS, GLU, GST>(p, acc, tile, slice, tiles_n, wm, wn, l31, hi, gate, stg, lnm, lnr);
+      big_epilogue<DT, BM, BN, TN, SPL, LNS, STATS, GLU, GST, !CONV>(p, acc, tile, slice, tiles_n, wm, wn, l31, hi, gate, stg, lnm, lnr);
     }
     TR(4)
     // store instructions this wave just issued, at least (see the first K-tile's wait above)

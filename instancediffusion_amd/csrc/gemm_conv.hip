@@ -988,6 +988,7 @@ extern "C" int idf_gemm(const idf_gemm_args* a, void* stream) {
   if ((a->epi & IDF_EPI_GEGLU_P32) && !(a->epi & IDF_EPI_GEGLU)) return IDF_E_ARG;
   if ((a->epi & IDF_EPI_ROWBIAS) && (!a->rowbias || a->rows_per_batch <= 0)) return IDF_E_ARG;
   if (a->epi & IDF_EPI_OUT_NCHW) return IDF_E_ARG;
+  if ((a->epi & IDF_EPI_QUICKGELU) && (a->epi & (IDF_EPI_SILU | IDF_EPI_GELU | IDF_EPI_GEGLU))) return IDF_E_ARG;   // one activation
   CoreParams p{};
   p.W = (const unsigned short*)a->W; p.ldw = a->ldw; p.strideW = a->strideW; p.N = a->N;
   p.A = (const unsigned short*)a->A; p.lda = a->lda; p.strideA = a->strideA; p.M = a->M; p.K = a->K;
@@ -1091,7 +1092,7 @@ static int conv3x3_launch(const idf_conv3x3_args* a, int pad_lo, void* stream) {
   if (a->stride != 1 && a->stride != 2) return IDF_E_ARG;
   if (a->upsample != 0 && a->upsample != 1) return IDF_E_ARG;
   if ((a->ldx % 8) || !aligned16(a->x) || !aligned16(a->W)) return IDF_E_ALIGN;
-  if (a->epi & (IDF_EPI_GEGLU | IDF_EPI_GATE)) return IDF_E_ARG;
+  if (a->epi & (IDF_EPI_GEGLU | IDF_EPI_GATE | IDF_EPI_QUICKGELU)) return IDF_E_ARG;   // QUICKGELU is an idf_gemm flag
   if ((a->epi & IDF_EPI_RES) && !a->res) return IDF_E_ARG;
   if ((a->epi & IDF_EPI_BIAS) && !a->bias) return IDF_E_ARG;
   CoreParams p{};

@@ -95,6 +95,10 @@ __device__ __forceinline__ void epilogue8(const CoreParams& p, int bz, int m, in
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = gelu_erf_f(v[e]);
   }
+  if (epi & IDF_EPI_QUICKGELU) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = quick_gelu_f(v[e]);
+  }
   if (epi & IDF_EPI_RES) {
     const unsigned short* rr = p.res + (size_t)bz * p.strideR + (size_t)m * p.ldr + n;
     const float gm = (epi & IDF_EPI_GATE) ? gate : 1.0f;

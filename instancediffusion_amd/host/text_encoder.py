@@ -1,7 +1,9 @@
 """Host mirror of ``ldm/modules/encoders/modules.py:FrozenCLIPEmbedder``.
 
-The text encoder runs ONCE per prompt, before the sampling path; it is a neighbour of the path, not part of it, so it
-stays on Hugging Face ``transformers`` (PyTorch-ROCm eager) exactly as in the reference.  Difference forced by the
+The text encoder runs ONCE per prompt, before the sampling path; it is a neighbour of the path, not part of it, so by default
+(``backend="hf"``) it stays on Hugging Face ``transformers`` (PyTorch-ROCm eager, fp32) exactly as in the reference.
+``backend="hip"`` keeps the tokenizer and runs the transformer on the HIP kernels instead
+(``instancediffusion_amd.clip_engine.CLIPTextEngine``, 16-bit storage in ``compute_dtype``).  Difference forced by the
 offline build environment: nothing is downloaded.  The CLIP-L/14 text transformer is built from its (fixed) config so
 that the checkpoint's ``['text_encoder']`` sub-dict -- which holds all its weights -- loads into it
 (``utils/checkpoint.py:246``); the BPE tokenizer needs the ``vocab.json`` / ``merges.txt`` of
@@ -27,8 +29,17 @@ class AbstractEncoder(nn.Module):
 class FrozenCLIPEmbedder(AbstractEncoder):
     """encoders/modules.py:144-172: CLIP text transformer -> last_hidden_state [B, 77, 768] (+ pooler_output)."""
 
-    def __init__(self, version="openai/clip-vit-large-patch14", device="cuda", max_length=77):
+    BACKENDS = ("hf", "hip")
+
+    def __init__(self, version="openai/clip-vit-large-patch14", device="cuda", max_length=77, backend=None):
         super().__init__()
+        if backend is None:                                  # the default: "hf", or what IDF_CLIP_BACKEND says
+            backend = os.environ.get("IDF_CLIP_BACKEND") or "hf"
+        if backend not in self.BACKENDS:
+            raise ValueError(f"FrozenCLIPEmbedder backend must be one of {self.BACKENDS}, got '{backend}'")
+        self.backend = backend
+        self.compute_dtype = torch.bfloat16     # 16-bit storage / MFMA input type of the HIP engine (or float16)
+        self._engine = None
         from transformers import CLIPTextConfig, CLIPTextModel
         self.version = os.environ.get("IDF_CLIP_PATH", version)
         self.transformer = CLIPTextModel(CLIPTextConfig(**CLIP_L14_TEXT))    # weights come from the checkpoint
@@ -68,7 +79,21 @@ class FrozenCLIPEmbedder(AbstractEncoder):
             remapped[k] = v
         if len(state_dict) and not (set(remapped) & mine):
             raise RuntimeError("text_encoder state dict matches none of the CLIP text transformer's parameters")
+        self._engine = None                                  # packed from the old weights
         return super().load_state_dict(remapped, strict=strict, **kw)
+
+    @property
+    def engine(self):
+        """The HIP executor of ``backend="hip"``, created on first use from the current weights and ``compute_dtype``."""
+        if self._engine is None or self._engine.dtype != self.compute_dtype:
+            try:
+                from ..clip_engine import CLIPTextEngine      # imports the C-ABI loader; raises if the .so is missing
+                self._engine = CLIPTextEngine(self.transformer, dtype=self.compute_dtype)
+            except (RuntimeError, OSError, KeyError) as e:
+                raise RuntimeError(
+                    "FrozenCLIPEmbedder(backend='hip') runs on the HIP kernels of libidf_gfx950.so on an MI355X, and that engine "
+                    f"could not be created ({e}); there is no fallback -- use backend='hf' for the transformers path") from e
+        return self._engine
 
     def freeze(self):
         self.transformer = self.transformer.eval()
@@ -85,6 +110,12 @@ class FrozenCLIPEmbedder(AbstractEncoder):
     def forward(self, text, return_pooler_output=False):
         enc = self.tokenizer(text, truncation=True, max_length=self.max_length, return_length=True,
                              return_overflowing_tokens=False, padding="max_length", return_tensors="pt")
+        if self.backend not in self.BACKENDS:
+            raise ValueError(f"FrozenCLIPEmbedder backend must be one of {self.BACKENDS}, got '{self.backend}'")
+        if self.backend == "hip":
+            z, pooled = self.engine.encode_ids(enc["input_ids"])
+            z, pooled = z.to(self.device), pooled.to(self.device)
+            return (z, pooled) if return_pooler_output else z
         outputs = self.transformer(input_ids=enc["input_ids"].to(self.device))
         z = outputs.last_hidden_state
         return (z, outputs.pooler_output) if return_pooler_output else z

@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import (EPI_BIAS, EPI_GATE, EPI_GEGLU, EPI_GEGLU_P32, EPI_GELU, EPI_LN_COL, EPI_LN_ROW, EPI_OUT_F32, EPI_OUT_NCHW,
-                   EPI_RES, EPI_ROWBIAS, EPI_SILU)
+                   EPI_QUICKGELU, EPI_RES, EPI_ROWBIAS, EPI_SILU)
 
 _DT = {torch.bfloat16: _lib.IDF_BF16, torch.float16: _lib.IDF_F16}
 
@@ -99,6 +99,8 @@ class HipOps:
             epi |= EPI_SILU
         elif act == "gelu":
             epi |= EPI_GELU
+        elif act == "quick_gelu":
+            epi |= EPI_QUICKGELU
         elif act is not None:
             raise ValueError(act)
         if geglu:
@@ -309,6 +311,30 @@ class HipOps:
             kbits1=None if (qbits is None or not n1) else kbits1.data_ptr(),
             strideKb1=0 if (qbits is None or not n1) else kbits1.stride(0))
         _lib.check(self.lib.idf_attention(C.byref(a), self._stream()), "idf_attention")
+        return out
+
+    def attention_causal(self, qkv, out, heads, T):
+        """Causal self-attention of the CLIP text transformer (``idf_attention_causal``): qkv [>= B*T, 3*C] view, columns q | k | v
+        as the fused projection leaves them, rows b*T + t; out [>= B*T, C] view.  B = out.shape[0] // T; head dim C / heads."""
+        Cc = out.shape[-1]
+        B = out.shape[0] // T
+        assert qkv.dim() == 2 and out.dim() == 2 and qkv.shape[-1] == 3 * Cc and qkv.shape[0] >= B * T and Cc % heads == 0
+        assert qkv.stride(-1) == 1 and out.stride(-1) == 1 and qkv.dtype == self.dtype and out.dtype == self.dtype
+        d = Cc // heads
+        _lib.check(self.lib.idf_attention_causal(_p(qkv), qkv.stride(0), _p(out), out.stride(0), B, T, heads, d, float(d) ** -0.5,
+                                                 self.dt, self._stream()), "idf_attention_causal")
+        return out
+
+    def clip_embed(self, ids_i32, tok_emb, pos_emb, out):
+        """out[b*T + t] = tok_emb[ids[b, t]] + pos_emb[t] (``idf_clip_embed``): ids int32 [B, T] contiguous, 16-bit tables
+        [vocab, C] / [>= T, C] contiguous, out [>= B*T, C] view.  Ids outside the table are clamped."""
+        B, T = ids_i32.shape
+        vocab, Cc = tok_emb.shape
+        assert ids_i32.dtype == torch.int32 and ids_i32.is_contiguous() and tok_emb.is_contiguous() and pos_emb.is_contiguous()
+        assert tok_emb.dtype == self.dtype and pos_emb.dtype == self.dtype and out.dtype == self.dtype
+        assert pos_emb.shape[0] >= T and pos_emb.shape[1] == Cc and out.shape[0] >= B * T and out.shape[1] == Cc and out.stride(-1) == 1
+        _lib.check(self.lib.idf_clip_embed(_p(ids_i32), _p(tok_emb), _p(pos_emb), _p(out), out.stride(0), B, T, Cc, vocab, self.dt,
+                                           self._stream()), "idf_clip_embed")
         return out
 
     def groupnorm(self, x, out, gamma, beta, eps, silu, partial=None):
