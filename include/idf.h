@@ -357,6 +357,26 @@ int idf_attention_causal(const void* qkv, int ld, void* out, int ldo, int B, int
 int idf_clip_embed(const int* ids, const void* tok_emb, const void* pos_emb, void* out, int ldo, int B, int T, int C, int vocab,
                    int dtype, void* stream);
 
+/* ---- CLIP image tower (eval/eval_attribute_binding.py:19-60: CLIPModel.get_image_features -> CLIPVisionTransformer) ------------------
+ * A ViT layer is the text layer with bidirectional attention; the other launches are idf_gemm / idf_layernorm.  Both entry points
+ * were added within ABI 5: new symbols only.
+ * idf_attention_qkv: the argument list and the qkv layout of idf_attention_causal;
+ * out[b*T + t][h*d + :] = softmax_j(scale * q_t . k_j) . v_j over ALL j < T.  Same kernel design (K and V^T of the head resident in
+ * LDS, here dynamic and sized by T: (ceil32(T) * 72 + 64 * (ceil32(T) + 4)) * 2 bytes, 78848 at the maximum).  Supported: d == 64 and
+ * 1 <= T <= IDF_ATTENTION_QKV_TMAX = 288 (ViT-L/14 at 224 px has T = 257; the 336-px model's T = 577 does not fit); anything else is
+ * IDF_E_UNSUPPORTED, a row start that is not 16-B aligned IDF_E_ALIGN, ld < 3*H*d / ldo < H*d / T < 1 / B < 1 IDF_E_ARG, all
+ * before any launch.  Keys in [T, ceil32(T)) are zero-filled in LDS and masked by select; nothing is read behind row B*T.
+ * idf_clip_patchify: pixels fp32 NCHW [B][3][S][S] -> patches 16-bit [B*G*G][ldp >= Kp], G = S / P, Kp = 3*P*P rounded up to a
+ * multiple of 64: patches[(b*G + gy)*G + gx][c*P*P + ky*P + kx] = pixels[b][c][gy*P + ky][gx*P + kx] (the column order of the
+ * flattened patch_embedding.weight [C][3][P][P]), one rounding, columns [3*P*P, Kp) zero.  The same launch writes the class rows
+ * x[b*(G*G + 1)][0:C] = cls_row[0:C] (16-bit; x has ldx >= C).  The patch rows of x then come from one batched idf_gemm
+ * (batch = B, M = G*G, strideA = G*G*ldp, out = x + ldx, strideO = (G*G + 1)*ldx, IDF_EPI_RES with res = position rows 1.., strideR =
+ * 0).  S % P == 0, P <= 32, else IDF_E_ARG; C % 8, ldp % 8, ldx % 8 and 16-B aligned 16-bit pointers, else IDF_E_ALIGN. */
+#define IDF_ATTENTION_QKV_TMAX 288
+int idf_attention_qkv(const void* qkv, int ld, void* out, int ldo, int B, int T, int H, int d, float scale, int dtype, void* stream);
+int idf_clip_patchify(const float* pixels, void* patches, int ldp, const void* cls_row, void* x, int ldx, int B, int S, int P, int C,
+                      int dtype, void* stream);
+
 /* ---- layout helpers ---------------------------------------------------------------------------------------*/
 int idf_cast_f32_to_16(const float* x, void* out, long long n, int dtype, void* stream);
 

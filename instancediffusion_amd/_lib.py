@@ -36,6 +36,7 @@ class GemmArgs(C.Structure):
 
 
 E_UNSUPPORTED = -3                       # IDF_E_UNSUPPORTED (include/idf.h)
+ATTENTION_QKV_TMAX = 288                 # IDF_ATTENTION_QKV_TMAX
 
 
 class ConvArgs(C.Structure):
@@ -94,6 +95,8 @@ SYMBOLS = {
     "idf_vae_posterior": (ci, [vp, vp, vp, vp, cf, vp, vp, ci, ci, ci, ll, vp]),
     "idf_attention_causal": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, cf, ci, vp]),
     "idf_clip_embed": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
+    "idf_attention_qkv": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, cf, ci, vp]),
+    "idf_clip_patchify": (ci, [vp, vp, ci, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
 }
 
 _lib = None

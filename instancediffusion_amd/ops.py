@@ -337,6 +337,34 @@ class HipOps:
                                            self._stream()), "idf_clip_embed")
         return out
 
+    ATTENTION_QKV_TMAX = _lib.ATTENTION_QKV_TMAX
+
+    def attention_qkv(self, qkv, out, heads, T):
+        """Bidirectional self-attention of the CLIP image tower (``idf_attention_qkv``): the layout of ``attention_causal``, every
+        query sees every key.  Head dim 64, T <= ``ATTENTION_QKV_TMAX``."""
+        Cc = out.shape[-1]
+        B = out.shape[0] // T
+        assert qkv.dim() == 2 and out.dim() == 2 and qkv.shape[-1] == 3 * Cc and qkv.shape[0] >= B * T and Cc % heads == 0
+        assert qkv.stride(-1) == 1 and out.stride(-1) == 1 and qkv.dtype == self.dtype and out.dtype == self.dtype
+        d = Cc // heads
+        _lib.check(self.lib.idf_attention_qkv(_p(qkv), qkv.stride(0), _p(out), out.stride(0), B, T, heads, d, float(d) ** -0.5,
+                                              self.dt, self._stream()), "idf_attention_qkv")
+        return out
+
+    def clip_patchify(self, pixels, patch, cls_row, x, patch_size):
+        """``idf_clip_patchify``: pixels fp32 [B, 3, S, S] contiguous -> patch [B*G*G, Kp] 16-bit view (G = S / patch_size, Kp = 3 P P
+        rounded up to 64, column order c*P*P + ky*P + kx, pad columns zero), and the class rows x[b*(G*G + 1)] = cls_row [C]."""
+        B, ch, S, S2 = pixels.shape
+        G = S // patch_size
+        Cc = cls_row.numel()
+        assert ch == 3 and S == S2 and pixels.dtype == torch.float32 and pixels.is_contiguous()
+        assert patch.dim() == 2 and patch.shape[0] >= B * G * G and patch.shape[1] == (3 * patch_size * patch_size + 63) // 64 * 64
+        assert x.dim() == 2 and x.shape[0] >= B * (G * G + 1) and x.shape[1] == Cc and x.stride(-1) == 1 and patch.stride(-1) == 1
+        assert patch.dtype == self.dtype and x.dtype == self.dtype and cls_row.dtype == self.dtype and cls_row.is_contiguous()
+        _lib.check(self.lib.idf_clip_patchify(_p(pixels), _p(patch), patch.stride(0), _p(cls_row), _p(x), x.stride(0), B, S, patch_size,
+                                              Cc, self.dt, self._stream()), "idf_clip_patchify")
+        return patch
+
     def groupnorm(self, x, out, gamma, beta, eps, silu, partial=None):
         """x/out [B, HW, C] (or [B,H,W,C]) contiguous.  ``partial``: the statistics of x are already there ([B, nchunks, 32, 2]
         fp32 (mean, M2) per row chunk, as a conv3x3 leaves them): only the normalise pass runs."""
