@@ -105,15 +105,26 @@ const char* idf_build_info(void);
  *   IDF_TUNE_GEGLU_ROW (round 6): the GEGLU projection of the C = 640 level (K = 640, N = 5120, epilogue BIAS | GEGLU | GEGLU_P32 |
  *     LN_ROW with the statistics handed in, M % 128 == 0, from two tiles per CU) on geglu640w_kernel: 0 = never, 1 = when the shape
  *     qualifies (default).  Env IDF_GEGLU_ROW.
+ *   IDF_TUNE_PROJ_ROW (knob 9; new enum values within ABI 5; id 8 stays unassigned -- it is the id the C-ABI test probes as
+ *     the unknown knob, idf_set_tuning(8, ..) == IDF_E_ARG): the N = K = 320 projections of the C = 320 level (batch 1, no vt_out,
+ *     M % 32 == 0, M >= 512 x the CU count -- two 256-row tiles per CU, the rule of IDF_TUNE_QKV_ROW; epilogue BIAS, BIAS | RES, BIAS | RES | GATE, or BIAS | LN_ROW with the statistics
+ *     handed in; each with or without out_stats) on proj320s_kernel (proj320_stream.hip: the weights resident in registers, the
+ *     rows streaming through LDS; out_stats come out final, no finalize pass): 0 = never (the launches of the library without this
+ *     kernel, bit for bit), 1 = when the shape qualifies (default).  Env IDF_PROJ_ROW.
+ *   IDF_TUNE_GEMM_BIG = 0 bypasses every row / streaming kernel above as well (QKV_ROW, GEGLU_ROW, PROJ_ROW): mode 0 is the
+ *     independent small-tile reference.
  */
 enum { IDF_TUNE_GEMM_BIG = 0, IDF_TUNE_ATTN2 = 1, IDF_TUNE_GEMM_RING = 2, IDF_TUNE_BIG_MIN_EFF = 3, IDF_TUNE_ATTN8 = 4, IDF_TUNE_MLP = 5,
-       IDF_TUNE_QKV_ROW = 6, IDF_TUNE_GEGLU_ROW = 7 };
+       IDF_TUNE_QKV_ROW = 6, IDF_TUNE_GEGLU_ROW = 7, IDF_TUNE_PROJ_ROW = 9 /* 8 unassigned */ };
 int idf_set_tuning(int knob, int value);
 /* Process-global launch counters (tests assert which kernel served a call).  Unknown stat: -1. */
 enum { IDF_STAT_GEMM_BIG_LAUNCHES = 0, IDF_STAT_ATTN2_LAUNCHES = 1, IDF_STAT_GEMM_RING_LAUNCHES = 2, IDF_STAT_ATTN8_LAUNCHES = 3,
        IDF_STAT_GN_EPI_LAUNCHES = 4 /* idf_conv3x3 calls whose gn_partial came out of the conv epilogue, not the statistics pass */,
        IDF_STAT_QKV_ROW_LAUNCHES = 6 /* fused q | k | v projections served by qkv320w_kernel (also counted in stat 0) */,
-       IDF_STAT_GEGLU_ROW_LAUNCHES = 7 /* GEGLU projections served by geglu640w_kernel (also counted in stat 0) */ };
+       IDF_STAT_GEGLU_ROW_LAUNCHES = 7 /* GEGLU projections served by geglu640w_kernel (also counted in stat 0) */,
+       IDF_STAT_PROJ_ROW_LAUNCHES = 8 /* N = K = 320 projections served by proj320s_kernel (also counted in stat 0) */,
+       IDF_STAT_PROJ_ROW_MIN_M = 9 /* not a counter: the least M proj320s_kernel takes on the current device under the current knobs
+                                      (0 = IDF_TUNE_PROJ_ROW or IDF_TUNE_GEMM_BIG is 0), so a caller can plan who produces ln_stats */ };
 long long idf_get_stat(int stat);
 
 /* ---- GEMM: out[M,N] = epi( A[M,K] . W[N,K]^T ) ----------------------------------------------------------

@@ -726,6 +726,7 @@ std::atomic<long long> idf_stat_gn_epi_launches{0};   // idf_conv3x3 calls whose
 std::atomic<long long> idf_stat_ring_launches{0};
 std::atomic<long long> idf_stat_gegluw_launches{0};   // GEGLU projections served by geglu640w_kernel (idf_get_stat)
 std::atomic<long long> idf_stat_qkvw_launches{0};     // fused q | k | v projections served by qkv320w_kernel (idf_get_stat)     // launches of the latency kernel (idf_get_stat)
+std::atomic<long long> idf_stat_projw_launches{0};    // N = K = 320 projections served by proj320s_kernel (idf_get_stat)
 int g_big_mode = -2;
 inline int gemm_big_mode() {
   if (g_big_mode == -2) {
@@ -959,6 +960,10 @@ extern "C" int idf_set_tuning(int knob, int value) {
     if (value < 0 || value > 1) return IDF_E_ARG;
     return idf_qkvw_set_mode(value);
   }
+  if (knob == IDF_TUNE_PROJ_ROW) {
+    if (value < 0 || value > 1) return IDF_E_ARG;
+    return idf_projw_set_mode(value);
+  }
   if (knob == IDF_TUNE_MLP) {
     if (value < 0 || value > 1) return IDF_E_ARG;
     return idf_mlp_set_mode(value);
@@ -974,6 +979,8 @@ extern "C" long long idf_get_stat(int stat) {
   if (stat == IDF_STAT_GN_EPI_LAUNCHES) return idf_stat_gn_epi_launches.load();
   if (stat == IDF_STAT_QKV_ROW_LAUNCHES) return idf_stat_qkvw_launches.load();
   if (stat == IDF_STAT_GEGLU_ROW_LAUNCHES) return idf_stat_gegluw_launches.load();
+  if (stat == IDF_STAT_PROJ_ROW_LAUNCHES) return idf_stat_projw_launches.load();
+  if (stat == IDF_STAT_PROJ_ROW_MIN_M) return gemm_big_mode() > 0 ? idf_projw_min_rows() : 0;
   return -1;
 }
 
@@ -1036,7 +1043,8 @@ extern "C" int idf_gemm(const idf_gemm_args* a, void* stream) {
     const bool self_ln = (a->epi & IDF_EPI_LN_ROW) && !a->ln_stats;
     if (self_ln && !a->ln_stats_out) return IDF_E_ARG;        // the fallback's second GEMM needs them somewhere
     p.vt_out = (unsigned short*)a->vt_out; p.ld_vt = a->ld_vt; p.vt_col0 = a->vt_col0;
-    {   // the row-resident kernel of the C = 320 level (qkv_fused.hip); counted with the persistent-kernel launches
+    // (IDF_TUNE_GEMM_BIG = 0 = "never a persistent kernel" bypasses the row kernels too: the small-tile kernels are the independent reference)
+    if (gemm_big_mode() > 0) {   // the row-resident kernel of the C = 320 level (qkv_fused.hip); counted with the persistent-kernel launches
       int r = idf_launch_qkv320w(p, a->dtype, s);
       if (r == IDF_BIG_UNSUPPORTED) r = idf_launch_qkv640w(p, a->dtype, s);       // ... and of the C = 640 level (qkv640_fused.hip)
       if (r != IDF_BIG_UNSUPPORTED) { if (r == 0) { ++idf_stat_big_launches; ++idf_stat_qkvw_launches; } return r; }
@@ -1070,10 +1078,16 @@ extern "C" int idf_gemm(const idf_gemm_args* a, void* stream) {
   // the output as before
   int parts = 0;
   // (whether the workspace holds the [M][parts][2] partials is checked where `parts` is chosen: idf_launch_big)
-  if ((a->epi & IDF_EPI_GEGLU) && batch == 1 && !a->out_stats) {
+  if ((a->epi & IDF_EPI_GEGLU) && batch == 1 && !a->out_stats && gemm_big_mode() > 0) {
     // the row-resident GEGLU kernel of the C = 640 level (geglu_fused.hip); counted with the persistent-kernel launches
     const int r = idf_launch_geglu640w(p, a->dtype, s);
     if (r != IDF_BIG_UNSUPPORTED) { if (r == 0) { ++idf_stat_big_launches; ++idf_stat_gegluw_launches; } return r; }
+  }
+  if (batch == 1 && gemm_big_mode() > 0) {
+    // the weights-resident streaming kernel of the N = K = 320 projections (proj320_stream.hip); counted with the persistent-kernel
+    // launches; it leaves the final out_stats itself (a whole output row lives in one workgroup): no finalize pass
+    const int r = idf_launch_proj320s(p, a->dtype, a->out_stats, a->out_stats_eps, s);
+    if (r != IDF_BIG_UNSUPPORTED) { if (r == 0) { ++idf_stat_big_launches; ++idf_stat_projw_launches; } return r; }
   }
   if (a->out_stats && batch == 1 && p.ws) p.stat_parts = p.ws;
   if (a->dtype == IDF_BF16) rc = launch<IDF_BF16, false>(p, batch, s, &parts);

@@ -159,6 +159,9 @@ int idf_launch_geglu640w(const idfcore::CoreParams& p, int dtype, hipStream_t s)
 int idf_gegluw_set_mode(int v);                         // 0 = never, 1 = when the shape qualifies; returns the previous mode
 int idf_launch_qkv640w(const idfcore::CoreParams& p, int dtype, hipStream_t s);   // qkv640_fused.hip
 int idf_qkvw_set_mode(int v);                           // both levels; 0 = never, 1 = when the shape qualifies; returns the previous mode
+int idf_launch_proj320s(const idfcore::CoreParams& p, int dtype, float* out_stats, float out_stats_eps, hipStream_t s);   // proj320_stream.hip; writes final out_stats itself
+int idf_projw_set_mode(int v);                          // 0 = never, 1 = when the shape qualifies; returns the previous mode
+int idf_projw_min_rows();                               // least M proj320s_kernel takes on the current device (two 256-row tiles per CU); 0 = knob off
 int idf_mlp_set_mode(int v);                            // mlp_fused.hip: 0 = mlp320_kernel, 1 = mlp320w_kernel; returns the previous mode
 int idf_big_min_eff_pct(int set);                        // automatic rule's occupancy bar in per cent (set < 0: query)
 int idf_num_cu();                                        // CUs of the current device (cached)

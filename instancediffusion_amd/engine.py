@@ -679,11 +679,26 @@ class UNetEngine:
         produced y: a GEGLU GEMM has 8-16 column tiles per row block, each of which would repeat the in-loop row sums --
         measured +15 % on those launches -- so here the separate 8-B-per-row pass is the cheaper form)."""
         ops = self.ops
-        if "w2p" in f and st is not None and LN_SELF_MODE != 2 and out_stats is None and M >= MLP_MIN_M and ops.mlp_supported(M, C):
+        if out_stats is None and st is not None and self._ff_fused(f, M, C):
             return ops.mlp_geglu(y, st, f["w1"], f["cd"], f["w2p"], f["l2"].b, y, gate=gate)
         mid = ops.gemm(y, f["w1"], self.buf("st.ffmid", (M, 4 * C)), bias=f["b1"], geglu=True, geglu_period=GEGLU_PERIOD,
                        ln_row=(None if LN_SELF_MODE == 2 else st, f["c1"]))
         return ops.gemm(mid, f["l2"].w, y, bias=f["l2"].b, res=y, gate=gate, out_stats=out_stats)
+
+    def _ff_fused(self, f, M, C):
+        """Does a feed-forward that is asked for no output statistics run as the one-launch fused MLP?"""
+        return "w2p" in f and LN_SELF_MODE != 2 and M >= MLP_MIN_M and self.ops.mlp_supported(M, C)
+
+    def _q_row(self, p, M, C, fuser_on):
+        """Is the cross-attention query of M rows handed its statistics instead of summing them in its K loop?  Where the
+        weights-resident streaming kernel takes that launch (the library's knobs and threshold: ``ops.proj_row_takes``) and
+        its producer emits them from an idf_gemm epilogue: attn1's out-projection (same kernel: final (mu, rstd) for free),
+        or the two-GEMM form of the fuser's feed-forward.  The fused MLP launch has no statistics output, so behind it the
+        query keeps its own sums."""
+        takes = getattr(self.ops, "proj_row_takes", None)
+        if LN_SELF_MODE != 1 or takes is None or not takes(M, C):
+            return False
+        return not (fuser_on and self._ff_fused(p["f_ff"], M, C))
 
     def _dup(self, t: torch.Tensor, role: str) -> torch.Tensor:
         """[n, ...] -> [2n, ...]: both halves a copy of t (the second half of a paired forward)."""
@@ -705,7 +720,7 @@ class UNetEngine:
         N, M = H * W, B * H * W
         g = ops.groupnorm(x, self.buf("gn", x.shape), p["norm"][0], p["norm"][1], 1e-6, False, partial=gnp)
         st = self.buf("st.stats", (M, 2), torch.float32)
-        own = self._ln_self(C)
+        own = self._ln_self(C) and not self._q_row(p, 2 * M if dup else M, C, fuser_on)
         own_qkv = self._qkv_self(C, N)
         # which producers emit statistics: `pqkv` those in front of a q | k | v projection, `pre` the one in front of the
         # cross-attention query, `ffs` those in front of a feed-forward
@@ -725,6 +740,8 @@ class UNetEngine:
                 ffs = st if ffs is not None else None
             else:
                 st = self.buf("st.stats", (2 * M, 2), torch.float32)
+                pre = st if pre is not None else None       # (written by a producer behind this point: f_ff with the fuser on)
+                pqkv = st if pqkv is not None else None
                 ffs = st if ffs is not None else None
             B, M = 2 * B, 2 * M
         # --- gated self attention over [visual ; grounding tokens] (attention.py:304-311): LN fuser.norm1 / norm2

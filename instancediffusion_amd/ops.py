@@ -159,6 +159,14 @@ class HipOps:
     # involution (it swaps positions 4..7 and 8..11)
     MLP_W2_PERM = (0, 1, 2, 3, 8, 9, 10, 11, 4, 5, 6, 7, 12, 13, 14, 15)
 
+    def proj_row_takes(self, M: int, C: int) -> bool:
+        """Does idf_gemm run an N = K = C projection of M rows on proj320s_kernel (weights resident, rows streaming)?  Asks the
+        library: its knobs (IDF_TUNE_PROJ_ROW, IDF_TUNE_GEMM_BIG) and its threshold for the current device."""
+        if C != 320 or M % 32:
+            return False
+        min_m = self.lib.idf_get_stat(_lib.IDF_STAT_PROJ_ROW_MIN_M)
+        return 0 < min_m <= M
+
     @staticmethod
     def mlp_supported(M: int, C: int) -> bool:
         """Shapes idf_mlp_geglu takes (the 64 x 64-latent blocks: C = 320, whole 128-row tiles)."""
