@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const unsigned short* __r
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
                                                       const float* __restrict__ partial, int HW, int C, int nchunks,
                                                       float eps, int silu, int nblk_x) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];     // scale[C], shift[C], mean[32], rstd[32]
+  extern __shared__ __attribute__((aligned(16))) float sm[];     // scale[C], beta[C], mean[32], rstd[32]
   float* sc = sm;
   float* sh = sm + C;
   float* mean = sm + (2 * C > 512 ? 2 * C : 512);                // the first 2 KB double as the fp64 reduction scratch
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const unsigned short* __r
   // threads share the work (8 chunk slices x 32 groups, fp64, fixed order -> bitwise reproducible) and no thread runs a
   // chain of 64 fp64 divisions in front of every row block.
   {
-    double* red = reinterpret_cast<double*>(sm);                  // [8][32], reused for scale/shift afterwards
+    double* red = reinterpret_cast<double*>(sm);                  // [8][32], reused for scale / beta afterwards
     const int g = tid & (GN_GROUPS - 1), part = tid / GN_GROUPS;
     const int rows_per_c = (HW + nchunks - 1) / nchunks;
     const double N = (double)HW * (double)cpg;
@@ -164,14 +164,15 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const unsigned short* __r
   }
   for (int ch = tid; ch < C; ch += 256) {
     const int g = ch / cpg;
-    const float w = gamma[ch] * rstd[g];
-    sc[ch] = w;
-    sh[ch] = beta[ch] - mean[g] * w;
+    sc[ch] = gamma[ch] * rstd[g];
+    sh[ch] = beta[ch];
   }
   __syncthreads();
   // Stream this block's row chunk with a FIXED channel chunk per thread (tx = 16-B column, ty = row lane): the 8
-  // scale/shift pairs live in registers for the whole row loop (the previous version re-read them from LDS per
+  // (mean, scale, beta) triples live in registers for the whole row loop (the previous version re-read them from LDS per
   // element with an 8-float lane stride: SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.86).
+  // y = (x - mean) * scale + beta, the mean taken off FIRST: folded into the shift (beta - mean * scale) the product is
+  // rounded at the size of mean / std, which a small output -- a group without variance gives beta itself -- does not survive.
   const int cpr = C >> 3;
   const int TX = cpr < 256 ? cpr : 256;
   const int TY = 256 / TX;
@@ -183,9 +184,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const unsigned short* __r
   unsigned short* ob = out + (size_t)b * HW * C;
   if (ty >= TY) return;
   for (int cc = tx; cc < cpr; cc += TX) {
-    float scr[8], shr[8];
+    float scr[8], shr[8], mr[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { scr[j] = sc[cc * 8 + j]; shr[j] = sh[cc * 8 + j]; }
+    for (int j = 0; j < 8; ++j) { scr[j] = sc[cc * 8 + j]; shr[j] = sh[cc * 8 + j]; mr[j] = mean[(cc * 8 + j) / cpg]; }
     // four rows in flight per thread (one 16-B load each before the first use): the kernel is latency-bound otherwise
     for (int r0 = r_begin + ty; r0 < r_end; r0 += UNR * TY) {
       u32x4 v[UNR];
@@ -202,7 +203,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const unsigned short* __r
         unpack8<DT>(v[u], f);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const float y = fmaf(f[j], scr[j], shr[j]);
+          const float y = fmaf(f[j] - mr[j], scr[j], shr[j]);
           f[j] = silu ? silu_f(y) : y;
         }
         *reinterpret_cast<u32x4*>(ob + (size_t)r * C + cc * 8) = pack8<DT>(f);
@@ -290,17 +291,38 @@ int gn_unroll() {
 }
 }  // namespace
 
+namespace {
+// Argument checks of the two halves, apart from the launches, so that idf_groupnorm can run BOTH before it launches anything:
+// their LDS limits differ (statistics 2 * TY * C floats, apply 2C + 64), and at C = 8192 only the second one refuses.
+int gn_stats_check(const void* x, const float* partial, int B, int HW, int C, int nchunks, int dtype, size_t* smem) {
+  if (!x || !partial) return IDF_E_ARG;
+  if (B <= 0 || HW <= 0 || C <= 0 || (C % 32) || (C % 8) || nchunks <= 0 || nchunks > HW) return IDF_E_ARG;
+  if (!aligned16(x)) return IDF_E_ALIGN;
+  const int cpr = C / 8, TX = cpr < 256 ? cpr : 256, TY = 256 / TX;
+  *smem = (size_t)2 * TY * C * sizeof(float);
+  if (*smem > 64 * 1024) return IDF_E_UNSUPPORTED;
+  if (dtype != IDF_BF16 && dtype != IDF_F16) return IDF_E_UNSUPPORTED;
+  return 0;
+}
+int gn_apply_check(const void* x, const void* out, const float* gamma, const float* beta, const float* partial, int B, int HW, int C,
+                   int nchunks, int dtype, size_t* smem) {
+  if (!x || !out || !gamma || !beta || !partial) return IDF_E_ARG;
+  if (B <= 0 || HW <= 0 || C <= 0 || (C % 32) || (C % 8) || nchunks <= 0 || nchunks > HW) return IDF_E_ARG;
+  if (!aligned16(x) || !aligned16(out)) return IDF_E_ALIGN;
+  *smem = (size_t)((2 * C > 512 ? 2 * C : 512) + 2 * GN_GROUPS) * sizeof(float);
+  if (*smem > 64 * 1024) return IDF_E_UNSUPPORTED;
+  if (dtype != IDF_BF16 && dtype != IDF_F16) return IDF_E_UNSUPPORTED;
+  return 0;
+}
+}  // namespace
+
 // The two halves of GroupNorm as separate entry points (round 5): the statistics pass can be replaced by a producer's
 // by-product (idf_conv3x3's gn_partial).  partial = [B][nchunks][32][2] fp32 (mean, M2); chunk k = rows [k rpc, (k + 1) rpc) of a
 // sample, rpc = ceil(HW / nchunks).
 extern "C" int idf_groupnorm_stats(const void* x, float* partial, int B, int HW, int C, int nchunks, int dtype, void* stream) {
-  if (!x || !partial) return IDF_E_ARG;
-  if (B <= 0 || HW <= 0 || C <= 0 || (C % 32) || (C % 8) || nchunks <= 0 || nchunks > HW) return IDF_E_ARG;
-  if (!aligned16(x)) return IDF_E_ALIGN;
+  size_t sm1 = 0;
+  if (const int rc = gn_stats_check(x, partial, B, HW, C, nchunks, dtype, &sm1)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int cpr = C / 8, TX = cpr < 256 ? cpr : 256, TY = 256 / TX;
-  const size_t sm1 = (size_t)2 * TY * C * sizeof(float);
-  if (sm1 > 64 * 1024) return IDF_E_UNSUPPORTED;
   dim3 g1(nchunks, B);
   const int unr = gn_unroll();
 #define IDF_GN_STATS(DT, U) hipLaunchKernelGGL((gn_stats_kernel<DT, U>), g1, dim3(256), sm1, s, (const unsigned short*)x, partial, HW, C, nchunks);
@@ -313,13 +335,10 @@ extern "C" int idf_groupnorm_stats(const void* x, float* partial, int B, int HW,
 
 extern "C" int idf_groupnorm_apply(const void* x, void* out, const float* gamma, const float* beta, const float* partial,
                                    int B, int HW, int C, int nchunks, float eps, int silu, int dtype, void* stream) {
-  if (!x || !out || !gamma || !beta || !partial) return IDF_E_ARG;
-  if (B <= 0 || HW <= 0 || C <= 0 || (C % 32) || (C % 8) || nchunks <= 0 || nchunks > HW) return IDF_E_ARG;
-  if (!aligned16(x) || !aligned16(out)) return IDF_E_ALIGN;
+  size_t sm2 = 0;
+  if (const int rc = gn_apply_check(x, out, gamma, beta, partial, B, HW, C, nchunks, dtype, &sm2)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int cpr = C / 8, TX = cpr < 256 ? cpr : 256, TY = 256 / TX;
-  const size_t sm2 = (size_t)((2 * C > 512 ? 2 * C : 512) + 2 * GN_GROUPS) * sizeof(float);
-  if (sm2 > 64 * 1024) return IDF_E_UNSUPPORTED;
   int nblk = (HW + TY * 8 - 1) / (TY * 8);                       // >= 8 rows per thread-row, <= 256 blocks per batch
   if (nblk < 1) nblk = 1;
   if (nblk > 256) nblk = 256;
@@ -339,6 +358,9 @@ extern "C" int idf_groupnorm(const void* x, void* out, const float* gamma, const
                              int B, int HW, int C, float eps, int silu, int dtype, void* stream) {
   if (!x || !out || !gamma || !beta || !ws) return IDF_E_ARG;
   const int nchunks = gn_nchunks(HW > 0 ? HW : 1);
+  size_t sm = 0;
+  if (const int rc = gn_stats_check(x, ws, B, HW, C, nchunks, dtype, &sm)) return rc;
+  if (const int rc = gn_apply_check(x, out, gamma, beta, ws, B, HW, C, nchunks, dtype, &sm)) return rc;   // before any launch
   const int rc = idf_groupnorm_stats(x, ws, B, HW, C, nchunks, dtype, stream);
   if (rc) return rc;
   return idf_groupnorm_apply(x, out, gamma, beta, ws, B, HW, C, nchunks, eps, silu, dtype, stream);

@@ -75,14 +75,15 @@ def test_engine_masked_forward_emulated(dtype, tol):
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------
-@pytest.mark.gpu
-@pytest.mark.parametrize("d,heads,nq,n1", [(40, 2, 4096, 184), (8, 8, 4096, 184), (40, 1, 300, 0), (80, 2, 256, 184)])
-def test_masked_attention_kernel(d, heads, nq, n1):
-    from instancediffusion_amd.ops import HipOps
-    from tests.emul_ops import EmulOps
-    ops, ref = HipOps(torch.bfloat16), EmulOps(torch.float32)
-    g = torch.Generator().manual_seed(5)
-    B, C = 2, d * heads
+MASKED_DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16}
+MASKED_TOL = {"bf16": 2.0 ** -6, "fp16": 2.0 ** -9}        # attention: twice one rounding of the largest element (2^-7 / 2^-10)
+
+
+def _masked_inputs(B, d, heads, nq, dtype, seed=5):
+    """Seeded q / k / V^T of both segments rounded to ``dtype`` (CPU), and random instance memberships as bit words: ~40 % of the
+    tokens in no instance (they only see themselves + unconditional keys)."""
+    g = torch.Generator().manual_seed(seed)
+    C = d * heads
     q, k0 = torch.randn(B, nq, C, generator=g), torch.randn(B, nq, C, generator=g)
     ld0, ld1 = (nq + 63) // 64 * 64, 192
     vt0 = torch.zeros(B, C, ld0)
@@ -90,7 +91,6 @@ def test_masked_attention_kernel(d, heads, nq, n1):
     k1 = torch.randn(B, 184, C, generator=g)
     vt1 = torch.zeros(B, C, ld1)
     vt1[:, :, :184] = torch.randn(B, C, 184, generator=g)
-    # random instance memberships: ~40 % of the tokens in no instance (they only see themselves + unconditional keys)
     obj = (torch.rand(B, nq, 5, generator=g) < 0.2)
     words = (obj.int() * (1 << torch.arange(5))).sum(-1).int()
     qb = (words | torch.tensor(-2 ** 31, dtype=torch.int32)).contiguous()
@@ -98,7 +98,20 @@ def test_masked_attention_kernel(d, heads, nq, n1):
     kb1 = torch.full((B, 192), -1, dtype=torch.int32)
     kb1[:, :5] = (1 << torch.arange(5)).int()
     kb1[1, 7] = 0                                                       # a key nobody sees
-    b16 = [t.to(torch.bfloat16) for t in (q, k0, vt0, k1, vt1)]
+    return [t.to(dtype) for t in (q, k0, vt0, k1, vt1)], qb, kb0, kb1
+
+
+# (40, 2, 77, 0) and (160, 1, 100, 184): a ragged query tile; the second also a ragged key tile and keys in segment 1
+@pytest.mark.gpu
+@pytest.mark.parametrize("d,heads,nq,n1", [(40, 2, 4096, 184), (8, 8, 4096, 184), (40, 1, 300, 0), (80, 2, 256, 184),
+                                           (40, 2, 77, 0), (160, 1, 100, 184)])
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+def test_masked_attention_kernel(dtype, d, heads, nq, n1):
+    from instancediffusion_amd.ops import HipOps
+    from tests.emul_ops import EmulOps
+    ops, ref = HipOps(MASKED_DTYPES[dtype]), EmulOps(torch.float32)
+    B, C = 2, d * heads
+    b16, qb, kb0, kb1 = _masked_inputs(B, d, heads, nq, MASKED_DTYPES[dtype])
     kw = dict(qbits=qb, kbits0=kb0) if not n1 else dict(k1=b16[3].float(), vt1=b16[4].float(), n1=n1, qbits=qb, kbits0=kb0, kbits1=kb1)
     want = ref.attention(b16[0].float(), b16[1].float(), b16[2].float(), nq, torch.empty(B, nq, C), heads, **kw)
     kwd = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in kw.items()}
@@ -107,11 +120,38 @@ def test_masked_attention_kernel(d, heads, nq, n1):
     out = ops.attention(b16[0].cuda(), b16[1].cuda(), b16[2].cuda(), nq, ops.empty((B, nq, C)), heads, **kwd)
     torch.cuda.synchronize()
     err = float((out.float().cpu() - want).abs().max() / want.abs().max())
-    assert torch.isfinite(out).all() and err < 2.0 ** -6, err
+    print(f"[parity] idf_attention masked {dtype} d={d} H={heads} nq={nq} n1={n1}: relmax {err:.2e} rel-rms {cases.rel_rms(out.float().cpu(), want):.2e}")
+    assert torch.isfinite(out).all() and err < MASKED_TOL[dtype], err
     # the mask matters: the unmasked result differs
     plain = ref.attention(b16[0].float(), b16[1].float(), b16[2].float(), nq, torch.empty(B, nq, C), heads,
                           **{k: v for k, v in kw.items() if "bits" not in k})
     assert float((plain - want).abs().max()) > 0.05
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n1", [0, 184])
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+def test_masked_query_with_no_group_sees_only_itself(dtype, n1):
+    """A query whose word is 0 sees its own token and nothing else, in either segment: its softmax is one-hot, every other key tile
+    takes the m_new = -inf branch of attention.hip, and the output row is its own column of V^T bit for bit.  First and last query,
+    and the two either side of a wave's 32-query boundary."""
+    from instancediffusion_amd.ops import HipOps
+    d, heads, nq, B = 40, 2, 100, 2
+    C = d * heads
+    ops = HipOps(MASKED_DTYPES[dtype])
+    (q, k0, vt0, k1, vt1), qb, kb0, kb1 = _masked_inputs(B, d, heads, nq, MASKED_DTYPES[dtype], seed=6)
+    alone = [0, 31, 32, nq - 1]
+    qb[:, alone] = 0
+    kw = dict(qbits=qb.cuda(), kbits0=kb0.cuda())
+    if n1:
+        kw.update(k1=k1.cuda(), vt1=vt1.cuda(), n1=n1, kbits1=kb1.cuda())
+    out = ops.attention(q.cuda(), k0.cuda(), vt0.cuda(), nq, ops.empty((B, nq, C)), heads, **kw)
+    torch.cuda.synchronize()
+    assert torch.isfinite(out).all()
+    for i in alone:
+        assert torch.equal(out[:, i].cpu(), vt0[:, :, i]), i
+    others = [i for i in range(nq) if i not in alone]
+    assert not torch.equal(out[:, others].cpu(), vt0[:, :, others].transpose(1, 2))
 
 
 @pytest.mark.gpu
