@@ -124,7 +124,10 @@ enum { IDF_STAT_GEMM_BIG_LAUNCHES = 0, IDF_STAT_ATTN2_LAUNCHES = 1, IDF_STAT_GEM
        IDF_STAT_GEGLU_ROW_LAUNCHES = 7 /* GEGLU projections served by geglu640w_kernel (also counted in stat 0) */,
        IDF_STAT_PROJ_ROW_LAUNCHES = 8 /* N = K = 320 projections served by proj320s_kernel (also counted in stat 0) */,
        IDF_STAT_PROJ_ROW_MIN_M = 9 /* not a counter: the least M proj320s_kernel takes on the current device under the current knobs
-                                      (0 = IDF_TUNE_PROJ_ROW or IDF_TUNE_GEMM_BIG is 0), so a caller can plan who produces ln_stats */ };
+                                      (0 = IDF_TUNE_PROJ_ROW or IDF_TUNE_GEMM_BIG is 0), so a caller can plan who produces ln_stats */,
+       IDF_STAT_ATTN_RES_LAUNCHES = 10 /* idf_attention calls served by the resident-key form of the 32-query kernel (<= 2 key tiles staged
+                                          once per workgroup, which walks several query blocks); a new enum value within ABI 5, as knob 9 was;
+                                          stat id 5 stays unassigned */ };
 long long idf_get_stat(int stat);
 
 /* ---- GEMM: out[M,N] = epi( A[M,K] . W[N,K]^T ) ----------------------------------------------------------
@@ -249,7 +252,8 @@ int idf_conv_in(const float* x_nchw, const float* w /*[C][Cin][3][3]*/, const fl
  * the gated self-attention concatenates visual tokens and the 184 grounding tokens (attention.py:307) -- the
  * two-segment form never materialises the concatenation and only computes the N_visual query rows that
  * attention.py:308 keeps.  V is supplied TRANSPOSED: vt[b][h*d + e][j] (ld = ldv, padded to a multiple of 64).
- * d % 8 == 0, d <= 160.
+ * d % 8 == 0, d <= 160, EXCEPT d = 104, 112, 136, 144 (7 or 9 K-steps of 16: the 32-query kernel has no instantiation for them),
+ * which return IDF_E_UNSUPPORTED before any launch.
  * Optional instance-visibility mask (the reference's masked gated self-attention, attention.py:187-255, reached with
  * efficient_attention=False + grounding_input["att_masks"]): 32-bit words per query / per key; query q may attend key j
  * iff (qbits[b][q] & kbits{0,1}[b][j]) != 0, or j is q's own token in segment 0 (the reference's 1e-9 diagonal).

@@ -407,6 +407,7 @@ int launch_attn(const AttnParams& p, int B, hipStream_t s) {
       if (p.d < 32 * MT) hipLaunchKernelGGL((attn_kernel<DT, KS, MT, true, true>), grid, block, 0, s, p, 1); \
       else hipLaunchKernelGGL((attn_kernel<DT, KS, MT, false, true>), grid, block, 0, s, p, 1); \
     } else if (res && qpw > 1) { \
+      ++idf_stat_attn_res_launches; \
       if (p.d < 32 * MT) hipLaunchKernelGGL((attn_kernel<DT, KS, MT, true, false, true>), grid_res, block, 0, s, p, qpw); \
       else hipLaunchKernelGGL((attn_kernel<DT, KS, MT, false, false, true>), grid_res, block, 0, s, p, qpw); \
     } else { \
@@ -423,12 +424,13 @@ int launch_attn(const AttnParams& p, int B, hipStream_t s) {
   IDF_ATTN_CASE(8, 4)    // d = 120, 128
   IDF_ATTN_CASE(10, 5)   // d = 152, 160
 #undef IDF_ATTN_CASE
-  return IDF_E_UNSUPPORTED;
+  return IDF_E_UNSUPPORTED;   // nks = 7, 9 (d = 104, 112, 136, 144): no instantiation; nothing was launched
 }
 
 }  // namespace
 
 std::atomic<long long> idf_stat_attn2_launches{0};
+std::atomic<long long> idf_stat_attn_res_launches{0};
 
 int g_attn2_mode = -2;
 int idf_attn2_mode() {

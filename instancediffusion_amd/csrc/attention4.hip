@@ -12,7 +12,7 @@
 //     Q = {-m, 0, ..., 0}, so the accumulator starts from the inline constant 0 (no -m register block, no v_mov) and comes
 //     out as (score - m) in log2 units.  m is rounded to the 16-bit storage type, which is harmless: softmax is shift
 //     invariant and the SAME m enters every P of the query and its denominator.
-//   * Overflow guard without a max: m is chosen so that the largest P of the first tile is 2^-SHIFT; after packing, the
+//   * Overflow guard without a max: m is chosen so that the largest P of the first tile is 2^-SHIFT (bf16 7, fp16 0); after packing, the
 //     32 packed P words of a lane are OR-ed (16 v_or3) and bit 14 of either half (<=> some P >= 2, in bf16 and fp16
 //     alike) sends the WAVE to the exact path, which recomputes the tile from the K tile still in LDS, raises m for the
 //     queries that grew and rescales their O rows.  The common tile costs {64 v_exp, 32 v_cvt_pk, 16 v_or3} of VALU.
@@ -64,15 +64,15 @@ struct FalseT { static constexpr bool value = false; };
 
 template <int DT> struct RefShift;           // after a re-base the largest P of a query is 2^-SHIFT (trigger: P >= 2)
 template <> struct RefShift<IDF_BF16> { static constexpr float v = 7.0f; };    // bf16: 8 exponent bits, shift is free
-// fp16 (round 5): 7, as bf16, instead of 1.  With 1 a wave left the common path whenever some score of a tile exceeded the
-// reference by 2 log2 units -- routine on real score distributions, and the reason the fp16 leg of the bench ran 5.6 % behind bf16
-// (harness at q / k amplitude 5: 641 TF with shift 1, 741 / 801 / 840 with 3 / 5 / 7, profiles/r05_attn8_first.log).
-// With 7 the largest P after a re-base is 2^-7: P below 2^-14 (2^-7 of the largest) become fp16 denormals, which the conversion
-// produces and the MFMA consumes exactly; their absolute rounding error (<= 2^-25) is far below the 2^-11 relative rounding of
-// the dominant P (2^-18 absolute), and the measured error against the fp32 reference is the same for every shift
-// (rel-RMS 4.6e-4 .. 4.9e-4 at amplitude 5, 5.0e-4 .. 5.4e-4 at 8).
+// fp16: 0 -- the reference value is the exact maximum of the tile it was taken from, never above the row's true maximum.  Rounds
+// 2-4 ran with 1, round 5 with 7 (as bf16) for speed: a wave leaves the common path whenever some score of a tile exceeds the
+// reference by SHIFT + 1 log2 units.  But fp16 has no exponent range to spare below 1: with the largest P of a query at 2^-7 every
+// P below 2^-7 of it is an fp16 denormal with an ABSOLUTE rounding error of 2^-25, i.e. up to 2^-11 of the P itself already at
+// 2^-14 of the largest.  A query whose first tile holds a key 7+ log2 units above the bulk then sums hundreds of keys at bf16
+// precision or worse: tests/test_attention_refs.py replays that arithmetic and finds elements at 2.8x the fp16 error bound
+// (first-tile spike) where 0 gives 0.29x.  attention4w.hip, which serves d = 40 by default, keeps its speed (it has no per-tile guard).
 #ifndef IDF_ATTN4_SHIFT_F16
-#define IDF_ATTN4_SHIFT_F16 7.0f
+#define IDF_ATTN4_SHIFT_F16 0.0f
 #endif
 template <> struct RefShift<IDF_F16> { static constexpr float v = IDF_ATTN4_SHIFT_F16; };
 

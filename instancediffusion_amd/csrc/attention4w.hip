@@ -138,7 +138,11 @@ __device__ unsigned long long idf_attn4w_trace_buf[4][8];
 #define TR_MARK(i) {}
 #endif
 
-template <int DT> struct RefShiftW { static constexpr float v = 7.0f; };   // after tile 0 the largest P of a query is 2^-7
+template <int DT> struct RefShiftW { static constexpr float v = 7.0f; };   // bf16: after tile 0 the largest P of a query is 2^-7
+// fp16: 0, as attention4.hip's RefShift (see there): below 2^-14 an fp16 P is a denormal, so the reference value must not sit above
+// the row's maximum.  The stream has no per-tile guard, so the only cost is head room: a later P overflows (block rerun on the
+// exact path) from 16 log2 units above the first tile's maximum instead of 23.
+template <> struct RefShiftW<IDF_F16> { static constexpr float v = 0.0f; };
 
 // NG = query groups (of 32) per wave.  4: one wave per SIMD (345 registers); 2: two waves per SIMD (two 4-wave workgroups per
 // CU, <= 256 registers) -- the same stream with 2 steps per block: a wave that stalls (LDS-DMA issue, barrier, prologue /

@@ -502,6 +502,8 @@ int idf_launch_attn8(const AttnParams& p, int B, int dtype, hipStream_t s) {
   if (!aligned16(p.out) || (p.ldo % 8) || (p.sO % 8) || !aligned16(p.q) || (p.ldq % 8) || (p.sQ % 8)) return IDF_ATTN2_UNSUPPORTED;
   // per-lane DMA offsets are 32-bit: a (batch, head) slice of K / V^T must stay below 2 GB
   if ((long long)KVT * p.ldk[0] * 2 >= (1ll << 31) || (long long)p.d * p.ldv[0] * 2 >= (1ll << 31)) return IDF_ATTN2_UNSUPPORTED;
+  if (p.n[1] > 0 && ((long long)KVT * p.ldk[1] * 2 >= (1ll << 31) || (long long)p.d * p.ldv[1] * 2 >= (1ll << 31)))
+    return IDF_ATTN2_UNSUPPORTED;               // segment 1 goes through the same 32-bit offsets (as attention4.hip / attention4w.hip check)
   if (dtype == IDF_BF16) return launch_attn8<IDF_BF16>(p, B, mode, s);
   if (dtype == IDF_F16) return launch_attn8<IDF_F16>(p, B, mode, s);
   return IDF_ATTN2_UNSUPPORTED;

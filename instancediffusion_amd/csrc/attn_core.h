@@ -37,6 +37,7 @@ struct AttnParams {
 #endif
 #include <atomic>
 extern std::atomic<long long> idf_stat_attn2_launches;   // process-global launch counter (idf_get_stat)
+extern std::atomic<long long> idf_stat_attn_res_launches;   // launches served by the resident-key (RES) instantiation of attn_kernel
 int idf_attn2_mode();
 int idf_attn2_set_mode(int v);
 int idf_launch_attn4(const idfattn::AttnParams& p, int B, int dtype, hipStream_t s);

@@ -981,6 +981,7 @@ extern "C" long long idf_get_stat(int stat) {
   if (stat == IDF_STAT_GEGLU_ROW_LAUNCHES) return idf_stat_gegluw_launches.load();
   if (stat == IDF_STAT_PROJ_ROW_LAUNCHES) return idf_stat_projw_launches.load();
   if (stat == IDF_STAT_PROJ_ROW_MIN_M) return gemm_big_mode() > 0 ? idf_projw_min_rows() : 0;
+  if (stat == IDF_STAT_ATTN_RES_LAUNCHES) return idf_stat_attn_res_launches.load();
   return -1;
 }
 
