@@ -12,14 +12,13 @@
 // the concatenation (reference attention.py:307).
 //
 // Roofline: MFMA-bound; algorithmic flops = 4 * nq * (n0+n1) * d per (b, h).
+// Block order, tile bookkeeping and the coalesced store tail are the family's (attn_core.h).
 #include "attn_core.h"
-#include <cstdlib>
 
 using namespace idfattn;
 
 namespace {
 
-constexpr int KVT = 64;            // kv rows per tile
 constexpr int VSTR = 72;           // V^T LDS row stride in elements (144 B = 9 x 16-B slots: conflict-free b128 reads)
 
 // NKS = ceil(d/16) K-steps of the QK^T contraction, NMT = ceil(d/32) 32-row tiles of O^T.
@@ -62,9 +61,8 @@ __global__ __launch_bounds__(256, (NKS <= 3 ? IDF_ATTN_MIN_WAVES : 1)) void attn
     const int gx = gridDim.x, gy = gridDim.y;
     const int total = gx * gy * (int)gridDim.z;
     if ((total & 7) == 0) {
-      int L = bx + gx * (h + gy * b);
-      L = (L & 7) * (total >> 3) + (L >> 3);
-      bx = L % gx;
+      const int L = xcd_block(bx + gx * (h + gy * b), total, true);
+      bx = L % gx;                                   // (not decode_block: on this 3-D grid it costs a division more per workgroup)
       const int r = L / gx;
       h = r % gy;
       b = r / gy;
@@ -100,9 +98,8 @@ __global__ __launch_bounds__(256, (NKS <= 3 ? IDF_ATTN_MIN_WAVES : 1)) void attn
   u32x4 qf[NKS];
   load_q(qb0, qf);
 
-  const int T0 = (p.n[0] + KVT - 1) / KVT;
-  const int T1 = (p.n[1] + KVT - 1) / KVT;
-  const int T = T0 + T1;
+  const int T0 = kv_tiles(p.n[0]);
+  const int T = T0 + kv_tiles(p.n[1]);
 
   // ---- staging roles (tile-invariant): thread -> K chunks (row, 16-B chunk) and V^T chunks (e row, 8-kv chunk)
   int k_lds[KCH_MAX], k_row[KCH_MAX], k_col[KCH_MAX];
@@ -131,9 +128,7 @@ __global__ __launch_bounds__(256, (NKS <= 3 ? IDF_ATTN_MIN_WAVES : 1)) void attn
   u32x4 kreg[KCH_MAX], vreg[VCH_MAX];
   unsigned breg = 0u;
   auto prefetch = [&](int t) {
-    const int seg = (t < T0) ? 0 : 1;
-    const int kv0 = (seg ? (t - T0) : t) * KVT;
-    const int n = p.n[seg];
+    const auto [seg, kv0, n] = kv_tile(p, t, T0);
     if (MASK && tid < KVT) breg = p.kbits[seg][(size_t)b * p.sKb[seg] + min(kv0 + tid, n - 1)];
     const int ldk = p.ldk[seg], ldv = p.ldv[seg];
     const unsigned short* kb = p.k[seg] + (size_t)b * p.sK[seg] + h * d;
@@ -142,7 +137,7 @@ __global__ __launch_bounds__(256, (NKS <= 3 ? IDF_ATTN_MIN_WAVES : 1)) void attn
     for (int i = 0; i < KCH_MAX; ++i) {
       u32x4 v = {0u, 0u, 0u, 0u};
       if (k_row[i] >= 0) {
-        const int kr = min(kv0 + k_row[i], n - 1);
+        const int kr = k_tail_row(kv0, k_row[i], n);
         v = *reinterpret_cast<const u32x4*>(kb + (size_t)kr * ldk + k_col[i]);
       }
       kreg[i] = v;
@@ -206,9 +201,8 @@ __global__ __launch_bounds__(256, (NKS <= 3 ? IDF_ATTN_MIN_WAVES : 1)) void attn
     const unsigned short* Kc = Kl + (t & 1) * KSZ;
     const unsigned short* Vc = Vl + (t & 1) * VSZ;
 
-    const int seg = (t < T0) ? 0 : 1;
-    const int kv0 = (seg ? (t - T0) : t) * KVT;
-    const int nvalid = p.n[seg] - kv0;            // >= 1
+    const auto [seg, kv0, n] = kv_tile(p, t, T0);
+    const int nvalid = n - kv0;                   // >= 1
     const bool two = nvalid > 32;                 // a tail of <= 32 keys (the 13 of the 77 text tokens): only the first half-tile
 
     // ---- S^T = K Q^T  (2 tiles of 32 kv rows)
@@ -344,26 +338,17 @@ __global__ __launch_bounds__(256, (NKS <= 3 ? IDF_ATTN_MIN_WAVES : 1)) void attn
 #pragma unroll
       for (int qd = 0; qd < 4; ++qd) {
         const int e = mt * 32 + 8 * qd + 4 * hi;
-        if (e < d) {
+        if (e < d) {   // (pack_o_rows written out, here and below: sharing one body makes the compiler merge the two epilogues)
           u32x2 pk = {pack2<DT>(o[mt][4 * qd] * inv, o[mt][4 * qd + 1] * inv),
                       pack2<DT>(o[mt][4 * qd + 2] * inv, o[mt][4 * qd + 3] * inv)};
           *reinterpret_cast<u32x2*>(orow + e) = pk;
         }
       }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    const int q0 = qblk * 128 + wave * 32;
+    lds_wave_fence();
     unsigned short* const obase = p.out + (size_t)b * p.sO + h * d;
-    const int nch = 4 * d;                            // 16-B chunks of the 32 x d block (dch per row)
-    for (int c = lane; c < nch; c += 64) {
-      const int row = c / dch, col = c - row * dch;
-      const u32x4 v = *reinterpret_cast<const u32x4*>(ow + c * 8);
-      if (q0 + row < p.nq) *reinterpret_cast<u32x4*>(obase + (size_t)(q0 + row) * p.ldo + col * 8) = v;
-    }
-    if (RES) {                                        // the staging block is rewritten by this wave's next query block
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-    }
+    for (int c = lane; c < 4 * d; c += 64)            // the 16-B chunks of the 32 x d block (dch per row; d is not a constant here)
+      store_chunk16(ow, obase, p.ldo, qblk * 128 + wave * 32, p.nq, c, dch);
+    if (RES) lds_wave_fence();                        // the staging block is rewritten by this wave's next query block
   } else if (qrow < p.nq) {
     unsigned short* op = p.out + (size_t)b * p.sO + (size_t)qrow * p.ldo + h * d;
 #pragma unroll
@@ -434,13 +419,7 @@ std::atomic<long long> idf_stat_attn_res_launches{0};
 
 int g_attn2_mode = -2;
 int idf_attn2_mode() {
-  if (g_attn2_mode == -2) {
-    // the environment may hold a value of an older ABI (modes 4..14 named kernels that left the library): out of range = default,
-    // the same range idf_set_tuning accepts
-    const char* e = getenv("IDF_ATTN2");
-    const int v = e ? atoi(e) : IDF_ATTN2_DEFAULT;
-    g_attn2_mode = (v < 0 || v > 6) ? IDF_ATTN2_DEFAULT : v;
-  }
+  if (g_attn2_mode == -2) g_attn2_mode = attn_mode_from_env("IDF_ATTN2", IDF_ATTN2_DEFAULT, 6);
   return g_attn2_mode;
 }
 int idf_attn2_set_mode(int v) { const int prev = idf_attn2_mode(); g_attn2_mode = v; return prev; }

@@ -28,6 +28,8 @@
 //     (685 KB at 4280 keys) stay in that XCD's L2 while its 16 blocks run.
 // Numerics contract as before: fp32 scores / accumulators, P rounded to the 16-bit type before P.V, denominator sums the
 // rounded P.  Requirements (else IDF_ATTN2_UNSUPPORTED and the caller falls back): d in {24, 40, 56}, n % 8 == 0, aligned.
+// The LDS-DMA primitives, block order, tile bookkeeping, tail source rules and the store tail are the family's (attn_core.h);
+// this file keeps the schedule.
 #include "attn_core.h"
 #include <cstdlib>
 
@@ -35,29 +37,8 @@ using namespace idfattn;
 
 namespace {
 
-__device__ __attribute__((aligned(128))) unsigned short idf_attn4_zero_page[64];
-__device__ __attribute__((aligned(16))) unsigned short idf_attn4_ones_page[2][8] = {
-    {0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80},      // bf16 1.0
-    {0x3c00, 0x3c00, 0x3c00, 0x3c00, 0x3c00, 0x3c00, 0x3c00, 0x3c00}};     // fp16 1.0
-
-constexpr int KVT = 64;
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// LDS-DMA issued through inline asm: the compiler's waitcnt pass otherwise puts s_waitcnt vmcnt(0) in front of the first
-// ds_read that follows ANY pending global_load_lds (it cannot tell the ring stages apart), which would serialise the
-// prefetch with the tile's own LDS reads.  Ordering is ours: `s_waitcnt vmcnt(0)` + s_barrier at the end of every tile.
-// lds = LDS byte address of lane 0's 16-B slot (lane i lands at lds + 16 i); it goes through M0.
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)p; }
-__device__ __forceinline__ void dma16_sv(const void* sbase /* wave-uniform */, unsigned voff, unsigned lds) {
-  lds = __builtin_amdgcn_readfirstlane(lds);         // wave-uniform by construction; make it provably so (an SGPR for M0)
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(voff), "s"(sbase) : "memory");   // M0 is ours here: nothing else in this kernel uses it (no movrel / GWS / sendmsg)
-}
-__device__ __forceinline__ void dma16_v(const void* addr /* per lane */, unsigned lds) {
-  lds = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds), "v"(addr) : "memory");   // M0 is ours here: nothing else in this kernel uses it (no movrel / GWS / sendmsg)
-}
+IDF_ATTN_ZERO_PAGE(idf_attn4_zero_page);
+IDF_ATTN_ONES_PAGE(idf_attn4_ones_page);
 
 struct TrueT { static constexpr bool value = true; };
 struct FalseT { static constexpr bool value = false; };
@@ -130,15 +111,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn4_kernel(const AttnParams p, c
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
 
-  // ---- XCD-aware block order: hardware block L runs on XCD L % 8; give every XCD a contiguous range of logical blocks
-  int L = blockIdx.x;
-  {
-    const int total = gridDim.x;
-    if ((xcd_order & 1) && (total & 7) == 0) L = (L & 7) * (total >> 3) + (L >> 3);
-  }
-  const int qb = L % nqb;
-  const int h = (L / nqb) % p.H;
-  const int b = L / (nqb * p.H);
+  int qb, h, b;
+  decode_block(xcd_block(blockIdx.x, gridDim.x, xcd_order & 1), nqb, p.H, qb, h, b);
 #ifdef IDF_ATTN_EXP
   // experiment (tools/ubench/attn_harness.hip, env IDF_ATTN_EXP = sleep_units | prio << 8): the second workgroup of every CU
   // (hardware blocks [256, 512) of the first dispatch round; later blocks inherit the slot phase of the one they replace) starts
@@ -187,9 +161,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn4_kernel(const AttnParams p, c
     }
   }
 
-  const int T0 = (p.n[0] + KVT - 1) / KVT;
-  const int T1 = (p.n[1] + KVT - 1) / KVT;
-  const int T = T0 + T1;
+  const int T0 = kv_tiles(p.n[0]);
+  const int T = T0 + kv_tiles(p.n[1]);
 
   // ---- DMA roles.  K: instruction i moves linear chunks 64 i .. 64 i + 63 of the tile: chunk c -> row c / DCH, column chunk
   // c % DCH.  V^T: instruction i moves rows 8 i .. 8 i + 7: lane -> row 8 i + (lane >> 3), LDS slot lane & 7 (holding the
@@ -211,16 +184,13 @@ __global__ __launch_bounds__(NW * 64, 2) void attn4_kernel(const AttnParams p, c
   }
 #pragma unroll
   for (int j = 0; j < V_PER_WAVE; ++j) {
-    const int row = (vwave + NW * j) * 8 + (lane >> 3);
-    voff0[j] = (unsigned)(row * p.ldv[0] + ((lane & 7) ^ ((row >> 1) & 7)) * 8) * 2u;
+    voff0[j] = vt_lane_off((vwave + NW * j) * 8, lane, p.ldv[0]);
   }
   auto cold_lane = [&]() { int l = lane; asm volatile("" : "+v"(l)); return l; };
 
   auto issue_k = [&](int t) {
     const int ln = cold_lane();
-    const int seg = (t < T0) ? 0 : 1;
-    const int kv0 = (seg ? (t - T0) : t) * KVT;
-    const int n = p.n[seg];
+    const auto [seg, kv0, n] = kv_tile(p, t, T0);
     const int ldk = p.ldk[seg];
     const char* kb = reinterpret_cast<const char*>(p.k[seg] + (size_t)b * p.sK[seg] + h * D);
     unsigned short* dst = Ks + (t % 3) * KSZ;
@@ -230,49 +200,31 @@ __global__ __launch_bounds__(NW * 64, 2) void attn4_kernel(const AttnParams p, c
       if (wave + NW * j < K_INST) {
         const int c = (wave + NW * j) * 64 + ln;
         const int row = c / DCH, col = (c - row * DCH) * 8;
-        // tail tile: rows beyond n are clamped to the last valid key
-        const int kr = full ? kv0 + row : min(kv0 + row, n - 1);
+        const int kr = full ? kv0 + row : k_tail_row(kv0, row, n);
         dma16_v(kb + ((size_t)kr * ldk + col) * 2, lds_addr(dst + (wave + NW * j) * 512));
       }
   };
-  // the ones-row group (rows D .. D+7 of the V^T image): row D = ones in the valid columns, zeros elsewhere
   auto issue_ones = [&](int stage, int nvalid) {
-    if (wave == NW / 2) {
-      const int ln = cold_lane();
-      const int row = D + (ln >> 3);
-      const int chunk = (ln & 7) ^ ((row >> 1) & 7);
-      const bool one = (row == D) && (chunk * 8 < nvalid);
-      const unsigned short* src = one ? idf_attn4_ones_page[DT == IDF_BF16 ? 0 : 1] : idf_attn4_zero_page + (ln & 7) * 8;
-      dma16_v(src, lds_addr(Vs + stage * VSZ + V_INST * 512));
-    }
+    if (wave == NW / 2)
+      dma16_v(ones_group_src<DT, D>(cold_lane(), nvalid, idf_attn4_ones_page, idf_attn4_zero_page), lds_addr(Vs + stage * VSZ + V_INST * 512));
   };
   auto issue_v = [&](int t) {
     const int ln = cold_lane();
-    const int seg = (t < T0) ? 0 : 1;
-    const int kv0 = (seg ? (t - T0) : t) * KVT;
-    const int n = p.n[seg];
+    const auto [seg, kv0, n] = kv_tile(p, t, T0);
     const int ldv = p.ldv[seg];
     const char* vb = reinterpret_cast<const char*>(p.vt[seg] + (size_t)b * p.sV[seg] + (size_t)(h * D) * ldv);
     unsigned short* dst = Vs + (t % VST) * VSZ;
     const char* base = vb + (size_t)kv0 * 2;
 #pragma unroll
     for (int j = 0; j < V_PER_WAVE; ++j)
-      if (vwave + NW * j < V_INST) {
-        const int row = (vwave + NW * j) * 8 + (ln >> 3);
-        const int chunk = (ln & 7) ^ ((row >> 1) & 7);
-        // tail tile: 8-key chunks beyond n (n % 8 == 0) come from the zero page
-        const bool valid = (kv0 + chunk * 8) < n;
-        const char* src = valid ? base + ((size_t)row * ldv + chunk * 8) * 2
-                                : reinterpret_cast<const char*>(idf_attn4_zero_page + (ln & 7) * 8);
-        dma16_v(src, lds_addr(dst + (vwave + NW * j) * 512));
-      }
+      if (vwave + NW * j < V_INST)
+        dma16_v(vt_chunk_src(base, (vwave + NW * j) * 8, ln, ldv, kv0, n, idf_attn4_zero_page), lds_addr(dst + (vwave + NW * j) * 512));
     // the ones row of this stage: restrict it for a tail tile, restore it when the stage last held a tail tile (tile t-VST)
     const bool tail = (kv0 + KVT > n);
     bool prev_tail = false;
     if (t >= VST) {
-      const int t2 = t - VST;
-      const int s2 = (t2 < T0) ? 0 : 1;
-      prev_tail = ((s2 ? (t2 - T0) : t2) + 1) * KVT > p.n[s2];
+      const KvTile prev = kv_tile(p, t - VST, T0);
+      prev_tail = prev.kv0 + KVT > prev.n;
     }
     if (tail || prev_tail) issue_ones(t % VST, tail ? n - kv0 : KVT);
   };
@@ -328,10 +280,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn4_kernel(const AttnParams p, c
     qf[g][NKS - 1][0] = hi ? neg_m : qf[g][NKS - 1][0];
     return d_eff;
   };
-  auto half_max = [&](float mx) -> float {           // max over the two lane halves that share a query
-    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-    return fmaxf(mx, __uint_as_float(hi ? sw[0] : sw[1]));
-  };
   // exact pass over the scores of group g (already relative to the current m): the tile's max maps to 2^-SHIFT
   auto rebase_scores = [&](const int g, const bool first) {
     float m0 = fmaxf(s[g][0][0], s[g][0][1]), m1 = fmaxf(s[g][1][0], s[g][1][1]);
@@ -340,7 +288,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn4_kernel(const AttnParams p, c
       m0 = fmaxf(fmaxf(m0, s[g][0][r]), s[g][0][r + 1]);
       m1 = fmaxf(fmaxf(m1, s[g][1][r]), s[g][1][r + 1]);
     }
-    const float d_eff = raise_m(g, half_max(fmaxf(m0, m1)) + RefShift<DT>::v, first);
+    const float d_eff = raise_m(g, half_max(fmaxf(m0, m1), hi) + RefShift<DT>::v, first);
 #pragma unroll
     for (int st = 0; st < 2; ++st)
 #pragma unroll
@@ -451,7 +399,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn4_kernel(const AttnParams p, c
             bad |= ((v & EXP_MASK) == EXP_MASK) | (((v >> 16) & EXP_MASK) == EXP_MASK);
             mx = fmaxf(mx, fmaxf(Elem<DT>::to_f32((unsigned short)(v & 0xffffu)), Elem<DT>::to_f32((unsigned short)(v >> 16))));
           }
-        mx = half_max(mx);
+        mx = half_max(mx, hi);
         // growth beyond 2^40 in one tile is left to the exact pass as well: the rescale factor 2^-(log2 mx + SHIFT) must stay
         // a normal fp32 number (v_exp_f32 flushes denormal results to 0, which would wipe O AND its denominator row)
         bad |= !(mx <= 0x1p40f);
@@ -541,21 +489,14 @@ __global__ __launch_bounds__(NW * 64, 2) void attn4_kernel(const AttnParams p, c
   }
 
   ATR_DUMP
-  // ---- normalise and store.  o[g][mt][r]: e = mt*32 + (r&3) + 8*(r>>2) + 4*hi, q = l31 of group g.
-  // row e = D of O^T holds the denominator: tile D/32, register 4*((D%32)/8) of the hi = 0 lanes.
-  // A lane owns ONE query row in 8-byte pieces: stored directly that is DCH 8-B stores per lane at a 2*ldo-byte lane
-  // stride -- store-issue-bound, and every 8-B piece is a partial 32-B sector (PMC: 4.6x the algorithmic write bytes,
-  // profiles/r02_rocprof/pmc_traffic_b64.json).  The K / V^T rings are dead here (every wave passed the last tile's
-  // barrier), so each wave transposes its 64 x D block through its own LDS slice and writes 16 B per lane with consecutive
-  // lanes on consecutive chunks of a row: a wave store instruction covers whole 2*D-byte row segments.
-  constexpr int sel = (D & 31) >> 3;
+  // ---- normalise and store.  The K / V^T rings are dead here (every wave passed the last tile's barrier), so each wave
+  // transposes its 64 x D block through its own LDS slice.
   unsigned short* const ow = smem + wave * (64 * D);       // wave-private [64 queries][D]
 #pragma unroll
   for (int g = 0; g < 2; ++g) {
-    const float lv = o[g][NMT - 1][4 * sel];
-    const float l_tot = __shfl(lv, l31, 64);               // broadcast from the hi = 0 lane of this query
-    const float inv = 1.0f / l_tot;
+    const float inv = 1.0f / denominator_from_ones_row(o[g][NMT - 1], D, l31);
     unsigned short* orow = ow + (g * 32 + l31) * D;
+    // (pack_o_rows, written out: through the helper this kernel allocates its registers differently -- one VGPR, one spill slot)
 #pragma unroll
     for (int mt = 0; mt < NMT; ++mt)
 #pragma unroll
@@ -568,19 +509,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn4_kernel(const AttnParams p, c
         }
       }
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the wave's own LDS writes, in order, before its reads
-  __builtin_amdgcn_wave_barrier();
-  {
-    const int q0 = qb * NT + wave * 64;
-    unsigned short* const obase = p.out + (size_t)b * p.sO + h * D;
-#pragma unroll
-    for (int j = 0; j < DCH; ++j) {
-      const int c = lane + 64 * j;                          // 16-B chunk of the block, row-major: byte offset 16 c
-      const int row = c / DCH, col = c - row * DCH;
-      const u32x4 v = *reinterpret_cast<const u32x4*>(ow + c * 8);
-      if (q0 + row < p.nq) *reinterpret_cast<u32x4*>(obase + (size_t)(q0 + row) * p.ldo + col * 8) = v;
-    }
-  }
+  store_block16<64, DCH>(ow, p.out + (size_t)b * p.sO + h * D, p.ldo, qb * NT + wave * 64, p.nq, lane);
 }
 
 inline int attn_exp() {
@@ -621,17 +550,7 @@ extern "C" int idf_attn_trace_read(unsigned long long* host /* [2][10] */) {
 
 int idf_launch_attn4(const AttnParams& p, int B, int dtype, hipStream_t s) {
   if (p.d != 24 && p.d != 40 && p.d != 56) return IDF_ATTN2_UNSUPPORTED;
-  if ((p.n[0] % 8) || (p.n[1] % 8)) return IDF_ATTN2_UNSUPPORTED;
-  if ((p.ldk[0] % 8) || (p.ldv[0] % 8) || (p.n[1] > 0 && ((p.ldk[1] % 8) || (p.ldv[1] % 8)))) return IDF_ATTN2_UNSUPPORTED;
-  if (!aligned16(p.k[0]) || !aligned16(p.vt[0]) || !aligned16(p.k[1]) || !aligned16(p.vt[1])) return IDF_ATTN2_UNSUPPORTED;
-  if ((p.sK[0] % 8) || (p.sV[0] % 8) || (p.sK[1] % 8) || (p.sV[1] % 8)) return IDF_ATTN2_UNSUPPORTED;
-  // the LDS-transposed epilogue stores O (and reads Q) as 16-B vectors: rows and batch strides must keep that alignment, else
-  // the 32-query kernel (8-B stores, idf_attention's own ldo % 4 contract) takes the launch
-  if (!aligned16(p.out) || (p.ldo % 8) || (p.sO % 8) || !aligned16(p.q) || (p.ldq % 8) || (p.sQ % 8)) return IDF_ATTN2_UNSUPPORTED;
-  // per-lane DMA offsets are 32-bit: a (batch, head) slice of K / V^T must stay below 4 GB
-  if ((long long)KVT * p.ldk[0] * 2 >= (1ll << 31) || (long long)(p.d + 8) * p.ldv[0] * 2 >= (1ll << 31)) return IDF_ATTN2_UNSUPPORTED;
-  if (p.n[1] > 0 && ((long long)KVT * p.ldk[1] * 2 >= (1ll << 31) || (long long)(p.d + 8) * p.ldv[1] * 2 >= (1ll << 31)))
-    return IDF_ATTN2_UNSUPPORTED;
+  if (!attn_dma_eligible(p, p.d + 8)) return IDF_ATTN2_UNSUPPORTED;        // + 8: the ones-row group
   if (dtype == IDF_BF16) return launch_attn4<IDF_BF16>(p, B, s);
   if (dtype == IDF_F16) return launch_attn4<IDF_F16>(p, B, s);
   return IDF_ATTN2_UNSUPPORTED;

@@ -19,9 +19,9 @@
 // The score block of a group is overwritten in place by the next block's K.Q^T (its exponentials were packed one step
 // earlier), so the four groups need 64 score registers, not 128; K fragments are read two blocks ahead, V^T fragments one.
 // K and V^T are both fetched TWO tiles ahead into 3-stage rings: one s_barrier per 64-key tile, nothing read from LDS right
-// behind it.
+// behind it.  The file-scope pieces (LDS-DMA primitives, block order, tile bookkeeping, tail source rules, store tail) are the
+// family's (attn_core.h); everything between FENCE / MFMA_DRAIN is this file's own.
 #include "attn_core.h"
-#include <cstdlib>
 #include <atomic>
 #include <type_traits>
 #include <utility>
@@ -30,29 +30,14 @@ using namespace idfattn;
 
 namespace {
 
-__device__ __attribute__((aligned(128))) unsigned short idf_attn4w_zero_page[64];
-__device__ __attribute__((aligned(16))) unsigned short idf_attn4w_ones_page[2][8] = {
-    {0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80},      // bf16 1.0
-    {0x3c00, 0x3c00, 0x3c00, 0x3c00, 0x3c00, 0x3c00, 0x3c00, 0x3c00}};     // fp16 1.0
+IDF_ATTN_ZERO_PAGE(idf_attn4w_zero_page);
+IDF_ATTN_ONES_PAGE(idf_attn4w_ones_page);
 
-constexpr int KVT = 64;        // keys per tile
 constexpr int D = 40, DCH = 5, NKS = 3, NMT = 2;
 constexpr int NW = 4;          // waves per workgroup
 constexpr int KSTG = 4096;     // K stage stride (elements): 64 rows x 40 (5120 B), ones fragments at bytes 5120 and 7680
 constexpr int VSZ = 64 * KVT;  // V^T stage (elements): 64 rows of 128 B, 16-B slot ^= (row >> 1) & 7
 constexpr int NST = 3;         // ring stages (K and V^T)
-
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)p; }
-// LDS-DMA through inline asm (see attention4.hip): ordering is ours -- s_waitcnt vmcnt(0) + s_barrier at the end of every tile.
-__device__ __forceinline__ void dma16_sv(const void* sbase /* wave-uniform */, unsigned voff, unsigned lds) {
-  lds = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(voff), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ void dma16_v(const void* addr /* per lane */, unsigned lds) {
-  lds = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds), "v"(addr) : "memory");
-}
-
 
 // ---- asm-owned accumulation registers.  The O^T accumulators (a[0:127]: tile (g, mt) at 16 (2 g + mt)) and the Q fragments
 // (a[128:175]: (g, ks) at 128 + 4 (3 g + ks)) live in AGPRs NAMED in the asm text: the register allocator never sees them, so
@@ -172,11 +157,7 @@ __global__ __launch_bounds__(NW * 64, NG == 4 ? 1 : 2) void attn4w_kernel(const 
   // hardware block L runs on XCD L % 8; every XCD gets a contiguous range of logical blocks (the query blocks of one (batch,
   // head) are consecutive: its K / V^T stay in that XCD's L2).  With PERSIST the stride gridDim.x is a multiple of 8.
   auto locate = [&](int blk, int& qb_, int& h_, int& b_) {
-    int L = blk;
-    if ((xcd_order & 1) && (total & 7) == 0) L = (L & 7) * (total >> 3) + (L >> 3);
-    qb_ = L % nqb;
-    h_ = (L / nqb) % p.H;
-    b_ = L / (nqb * p.H);
+    decode_block(xcd_block(blk, total, xcd_order & 1), nqb, p.H, qb_, h_, b_);
   };
 
   // Pad rows of the V^T stages (rows D .. 63 of every O^T tile must be finite: row D = ones, the others zero) and the ones
@@ -196,9 +177,8 @@ __global__ __launch_bounds__(NW * 64, NG == 4 ? 1 : 2) void attn4w_kernel(const 
   };
   if (tid == 0) *redo_flag = 0;
 
-  const int T0 = (p.n[0] + KVT - 1) / KVT;
-  const int T1 = (p.n[1] + KVT - 1) / KVT;
-  const int T = T0 + T1;
+  const int T0 = kv_tiles(p.n[0]);
+  const int T = T0 + kv_tiles(p.n[1]);
 
   // ---- DMA roles (as attention4.hip): K instruction i (linear 16-B chunks 64 i .. 64 i + 63 of the tile) by wave i % 4,
   // V^T instruction i (rows 8 i .. 8 i + 7) by wave (i + 1) % 4: 3 / 3 / 2 / 2 per wave and tile.  `so` = byte offset of the
@@ -211,9 +191,7 @@ __global__ __launch_bounds__(NW * 64, NG == 4 ? 1 : 2) void attn4w_kernel(const 
 
   auto issue_k = [&](int t, int bb, int hh, unsigned so) {
     const int ln = cold_lane();
-    const int seg = (t < T0) ? 0 : 1;
-    const int kv0 = (seg ? (t - T0) : t) * KVT;
-    const int n = p.n[seg];
+    const auto [seg, kv0, n] = kv_tile(p, t, T0);
     const int ldk = p.ldk[seg];
     const char* kb = reinterpret_cast<const char*>(p.k[seg] + (size_t)bb * p.sK[seg] + hh * D);
     unsigned short* dst = Ks + (so >> 1);
@@ -223,25 +201,18 @@ __global__ __launch_bounds__(NW * 64, NG == 4 ? 1 : 2) void attn4w_kernel(const 
       if (wave + NW * j < K_INST) {
         const int c = (wave + NW * j) * 64 + ln;
         const int row = c / DCH, col = (c - row * DCH) * 8;
-        const int kr = full ? kv0 + row : min(kv0 + row, n - 1);     // tail: clamped duplicates of the last valid key
+        const int kr = full ? kv0 + row : k_tail_row(kv0, row, n);     // tail: clamped duplicates of the last valid key
         dma16_v(kb + ((size_t)kr * ldk + col) * 2, lds_addr(dst + (wave + NW * j) * 512));
       }
   };
   auto issue_ones = [&](unsigned so, int nvalid) {
     if (wave == NW / 2) {
-      const int ln = cold_lane();
-      const int row = D + (ln >> 3);
-      const int chunk = (ln & 7) ^ ((row >> 1) & 7);
-      const bool one = (row == D) && (chunk * 8 < nvalid);
-      const unsigned short* src = one ? idf_attn4w_ones_page[DT == IDF_BF16 ? 0 : 1] : idf_attn4w_zero_page + (ln & 7) * 8;
-      dma16_v(src, lds_addr(Vs + (so >> 1) + V_INST * 512));
+      dma16_v(ones_group_src<DT, D>(cold_lane(), nvalid, idf_attn4w_ones_page, idf_attn4w_zero_page), lds_addr(Vs + (so >> 1) + V_INST * 512));
     }
   };
   auto issue_v = [&](int t, int bb, int hh, unsigned so) {
     const int ln = cold_lane();
-    const int seg = (t < T0) ? 0 : 1;
-    const int kv0 = (seg ? (t - T0) : t) * KVT;
-    const int n = p.n[seg];
+    const auto [seg, kv0, n] = kv_tile(p, t, T0);
     const int ldv = p.ldv[seg];
     const char* vb = reinterpret_cast<const char*>(p.vt[seg] + (size_t)bb * p.sV[seg] + (size_t)(hh * D) * ldv);
     unsigned short* dst = Vs + (so >> 1);
@@ -249,12 +220,7 @@ __global__ __launch_bounds__(NW * 64, NG == 4 ? 1 : 2) void attn4w_kernel(const 
 #pragma unroll
     for (int j = 0; j < V_PER_WAVE; ++j)
       if (vwave + NW * j < V_INST) {
-        const int row = (vwave + NW * j) * 8 + (ln >> 3);
-        const int chunk = (ln & 7) ^ ((row >> 1) & 7);
-        const bool valid = (kv0 + chunk * 8) < n;                    // tail: 8-key chunks beyond n come from the zero page
-        const char* src = valid ? base + ((size_t)row * ldv + chunk * 8) * 2
-                                : reinterpret_cast<const char*>(idf_attn4w_zero_page + (ln & 7) * 8);
-        dma16_v(src, lds_addr(dst + (vwave + NW * j) * 512));
+        dma16_v(vt_chunk_src(base, (vwave + NW * j) * 8, ln, ldv, kv0, n, idf_attn4w_zero_page), lds_addr(dst + (vwave + NW * j) * 512));
       }
     // the ones row of this stage: restrict it for a tail tile, restore it when the stage last held a tail tile
     const bool tail = (kv0 + KVT > n);
@@ -287,10 +253,6 @@ __global__ __launch_bounds__(NW * 64, NG == 4 ? 1 : 2) void attn4w_kernel(const 
     for (int mt = 0; mt < NMT; ++mt)
 #pragma unroll
       for (int st = 0; st < 2; ++st) dst[mt][st] = lds128(vs_base + stage_off + vA[half * 2 + st] + mt * 4096);
-  };
-  auto half_max = [&](float mx) -> float {
-    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-    return fmaxf(mx, __uint_as_float(hi ? sw[0] : sw[1]));
   };
   // raw Q fragment (B operand) of one query group and K-step: lane holds q = l31, e = 16*ks + 8*hi .. +7 (zero beyond D)
   auto load_q_raw = [&](const int g, const int ks, int qbb, int hh, int bb) -> u32x4 {
@@ -426,7 +388,7 @@ __global__ __launch_bounds__(NW * 64, NG == 4 ? 1 : 2) void attn4w_kernel(const 
           m1 = fmaxf(fmaxf(m1, s1[r]), s1[r + 1]);
         }
         // keys beyond n in a tail tile are clamped duplicates of a valid key: they cannot raise the max
-        const float m = Elem<DT>::to_f32(Elem<DT>::from_f32(half_max(fmaxf(m0, m1)) + RefShiftW<DT>::v));
+        const float m = Elem<DT>::to_f32(Elem<DT>::from_f32(half_max(fmaxf(m0, m1), hi) + RefShiftW<DT>::v));
         u32x4 pk[4];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -504,8 +466,7 @@ __global__ __launch_bounds__(NW * 64, NG == 4 ? 1 : 2) void attn4w_kernel(const 
             dlds[j] = (unsigned)__builtin_amdgcn_readfirstlane(ki[j] * 1024);
           } else {
             const int vv = vi[j] >= 0 ? vi[j] : 0;
-            const int row = vv * 8 + (lane >> 3);
-            doff[j] = (unsigned)(row * p.ldv[0] + ((lane & 7) ^ ((row >> 1) & 7)) * 8) * 2u;
+            doff[j] = vt_lane_off(vv * 8, lane, p.ldv[0]);
             dlds[j] = (unsigned)__builtin_amdgcn_readfirstlane(NST * KSTG * 2 + vv * 1024);
           }
         }
@@ -711,7 +672,7 @@ __global__ __launch_bounds__(NW * 64, NG == 4 ? 1 : 2) void attn4w_kernel(const 
             m1 = fmaxf(fmaxf(m1, sx[1][r]), sx[1][r + 1]);
           }
           // scores are relative to the current m (through the -m slot); raise it so that the tile's maximum maps to 2^-SHIFT
-          const float want = half_max(fmaxf(m0, m1)) + RefShiftW<DT>::v;
+          const float want = half_max(fmaxf(m0, m1), hi) + RefShiftW<DT>::v;
           const float delta = t == 0 ? want : fmaxf(want, 0.0f);
           const float m_new = Elem<DT>::to_f32(Elem<DT>::from_f32(m_run + delta));
           const float d_eff = m_new - m_run;
@@ -758,19 +719,7 @@ __global__ __launch_bounds__(NW * 64, NG == 4 ? 1 : 2) void attn4w_kernel(const 
       continue;
     }
 
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    {
-      const int q0 = qb * QB + wave * (NG * 32);
-      unsigned short* const obase = p.out + (size_t)b * p.sO + h * D;
-#pragma unroll
-      for (int j = 0; j < NG * 32 * DCH / 64; ++j) {
-        const int c = lane + 64 * j;
-        const int row = c / DCH, col = c - row * DCH;
-        const u32x4 v = *reinterpret_cast<const u32x4*>(ow + c * 8);
-        if (q0 + row < p.nq) *reinterpret_cast<u32x4*>(obase + (size_t)(q0 + row) * p.ldo + col * 8) = v;
-      }
-    }
+    store_block16<NG * 32, DCH>(ow, p.out + (size_t)b * p.sO + h * D, p.ldo, qb * QB + wave * (NG * 32), p.nq, lane);
     TR_MARK(6)
 #ifdef IDF_ATTN4W_TRACE
     tr_acc[7] += 1;
@@ -833,14 +782,7 @@ extern "C" int idf_attn4w_trace_read(unsigned long long* host /* [4][4] */) {
 
 int idf_launch_attn4w(const AttnParams& p, int B, int dtype, int variant /* IDF_TUNE_ATTN2 value: 4, 5, 6 */, hipStream_t s) {
   if (p.d != 40) return IDF_ATTN2_UNSUPPORTED;
-  if ((p.n[0] % 8) || (p.n[1] % 8)) return IDF_ATTN2_UNSUPPORTED;
-  if ((p.ldk[0] % 8) || (p.ldv[0] % 8) || (p.n[1] > 0 && ((p.ldk[1] % 8) || (p.ldv[1] % 8)))) return IDF_ATTN2_UNSUPPORTED;
-  if (!aligned16(p.k[0]) || !aligned16(p.vt[0]) || !aligned16(p.k[1]) || !aligned16(p.vt[1])) return IDF_ATTN2_UNSUPPORTED;
-  if ((p.sK[0] % 8) || (p.sV[0] % 8) || (p.sK[1] % 8) || (p.sV[1] % 8)) return IDF_ATTN2_UNSUPPORTED;
-  if (!aligned16(p.out) || (p.ldo % 8) || (p.sO % 8) || !aligned16(p.q) || (p.ldq % 8) || (p.sQ % 8)) return IDF_ATTN2_UNSUPPORTED;
-  if ((long long)KVT * p.ldk[0] * 2 >= (1ll << 31) || (long long)(p.d + 8) * p.ldv[0] * 2 >= (1ll << 31)) return IDF_ATTN2_UNSUPPORTED;
-  if (p.n[1] > 0 && ((long long)KVT * p.ldk[1] * 2 >= (1ll << 31) || (long long)(p.d + 8) * p.ldv[1] * 2 >= (1ll << 31)))
-    return IDF_ATTN2_UNSUPPORTED;
+  if (!attn_dma_eligible(p, p.d + 8)) return IDF_ATTN2_UNSUPPORTED;        // + 8: the ones-row group
   if (dtype == IDF_BF16) return launch_attn4w<IDF_BF16>(p, B, variant, s);
   if (dtype == IDF_F16) return launch_attn4w<IDF_F16>(p, B, variant, s);
   return IDF_ATTN2_UNSUPPORTED;

@@ -27,40 +27,17 @@
 // ring); d = 160 has no registers for that and reads its K fragments inside the K.Q^T loop from a 2-stage ring.
 // Numerics contract as the other variants: fp32 scores / accumulators, P rounded to the 16-bit type before P.V.
 // Requirements (else IDF_ATTN2_UNSUPPORTED and the caller falls back): d in {80, 160}, n0 % 8 == n1 % 8 == 0, no mask.
+// The LDS-DMA primitives, block order, tile bookkeeping, tail source rules and the epilogue are the family's (attn_core.h);
+// this file keeps the schedule.
 #include "attn_core.h"
-#include <cstdlib>
 
 using namespace idfattn;
 
 namespace {
 
-__device__ __attribute__((aligned(128))) unsigned short idf_attn8_zero_page[64];
+IDF_ATTN_ZERO_PAGE(idf_attn8_zero_page);
 
-constexpr int KVT = 64;
 constexpr float DEFER = 6.0f;                        // log2 units a tile maximum may exceed the reference without a rescale
-
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)p; }
-// lds = LDS byte address of lane 0's 16-B slot (lane i lands at lds + 16 i); it goes through M0.  M0 cannot be declared in the
-// clobber list (hipcc: "reserved register"); it is ours here -- nothing else in this kernel uses it (no movrel / GWS / sendmsg,
-// no LDS-DMA builtin) and every asm statement that reads it writes it first.
-__device__ __forceinline__ const void* uniform_ptr(const void* p) {      // provably wave-uniform (an SGPR pair for the asm operand)
-  const unsigned long long a = (unsigned long long)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-  return (const void*)(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ void dma16_sv(const void* sbase /* wave-uniform */, unsigned voff, unsigned lds) {
-  lds = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(voff), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ void dma16_v(const void* addr /* per lane */, unsigned lds) {
-  lds = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds), "v"(addr) : "memory");
-}
-__device__ __forceinline__ float max3f(float a, float b, float c) {
-  float r;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
 
 template <int DT, int D, int NW, int MODE>
 __global__ __launch_bounds__(NW * 64, 2) void attn8_kernel(const AttnParams p, const int nqb, const int xcd_order) {
@@ -91,15 +68,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn8_kernel(const AttnParams p, c
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
 
-  // ---- XCD-aware block order: hardware block L runs on XCD L % 8; give every XCD a contiguous range of logical blocks
-  int L = blockIdx.x;
-  {
-    const int total = gridDim.x;
-    if ((xcd_order & 1) && (total & 7) == 0) L = (L & 7) * (total >> 3) + (L >> 3);
-  }
-  const int qb = L % nqb;
-  const int h = (L / nqb) % p.H;
-  const int b = L / (nqb * p.H);
+  int qb, h, b;
+  decode_block(xcd_block(blockIdx.x, gridDim.x, xcd_order & 1), nqb, p.H, qb, h, b);
 
   // zero the pad rows of the V^T ring once (rows D.. of the O^T tile must be finite zeros), then the ones row
   if constexpr (VROWS > D) {
@@ -139,9 +109,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn8_kernel(const AttnParams p, c
   const float c = p.scale_log2;
 #endif
 
-  const int T0 = (p.n[0] + KVT - 1) / KVT;
-  const int T1 = (p.n[1] + KVT - 1) / KVT;
-  const int T = T0 + T1;
+  const int T0 = kv_tiles(p.n[0]);
+  const int T = T0 + kv_tiles(p.n[1]);
   const int F0 = p.n[0] / KVT;                       // full tiles of segment 0
 
   // ---- DMA roles.  The tile's N_INST instructions (K: instruction i moves LDS slots 64 i .. 64 i + 63 of the stage, slot s ->
@@ -161,7 +130,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn8_kernel(const AttnParams p, c
       col = col == DCH ? 0 : col;
       o = (unsigned)(row * p.ldk[0] + col * 8) * 2u;
     } else if (g < N_INST) {
-      const int row = (g - K_INST) * 8 + (lane >> 3);
+      const int row = (g - K_INST) * 8 + (lane >> 3);      // (vt_lane_off, written out: through the helper the d = 160 form takes a register more)
       o = (unsigned)(row * p.ldv[0] + ((lane & 7) ^ ((row >> 1) & 7)) * 8) * 2u;
     }
     off0[j] = o;
@@ -170,9 +139,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn8_kernel(const AttnParams p, c
   // generic (cold) issue of tile t's K (do_k) and / or V^T (do_v) loads
   auto issue_cold = [&](const int t, const bool do_k, const bool do_v) {
     const int ln = cold_lane();
-    const int seg = (t < T0) ? 0 : 1;
-    const int kv0 = (seg ? (t - T0) : t) * KVT;
-    const int n = p.n[seg];
+    const auto [seg, kv0, n] = kv_tile(p, t, T0);
     const int ldk = p.ldk[seg], ldv = p.ldv[seg];
     const char* kb = reinterpret_cast<const char*>(p.k[seg] + (size_t)b * p.sK[seg] + h * D);
     const char* vb = reinterpret_cast<const char*>(p.vt[seg] + (size_t)b * p.sV[seg] + (size_t)(h * D) * ldv) + (size_t)kv0 * 2;
@@ -187,17 +154,12 @@ __global__ __launch_bounds__(NW * 64, 2) void attn8_kernel(const AttnParams p, c
           const int row = s / KCH;
           int col = s - row * KCH;
           col = col == DCH ? 0 : col;
-          const int kr = min(kv0 + row, n - 1);        // tail tile: rows beyond n are clamped to the last valid key
+          const int kr = k_tail_row(kv0, row, n);
           dma16_v(kb + ((size_t)kr * ldk + col * 8) * 2, lds_addr(kdst + g * 512));
         }
       } else if (g < N_INST) {
         if (do_v) {
-          const int row = (g - K_INST) * 8 + (ln >> 3);
-          const int chunk = (ln & 7) ^ ((row >> 1) & 7);
-          const bool valid = (kv0 + chunk * 8) < n;    // n % 8 == 0: a chunk is valid or invalid as a whole
-          const char* src = valid ? vb + ((size_t)row * ldv + chunk * 8) * 2
-                                  : reinterpret_cast<const char*>(idf_attn8_zero_page + (ln & 7) * 8);
-          dma16_v(src, lds_addr(vdst + (g - K_INST) * 512));
+          dma16_v(vt_chunk_src(vb, (g - K_INST) * 8, ln, ldv, kv0, n, idf_attn8_zero_page), lds_addr(vdst + (g - K_INST) * 512));
         }
       }
     }
@@ -263,10 +225,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn8_kernel(const AttnParams p, c
         }
     }
   };
-  auto half_max = [&](float mx) -> float {           // max over the two lane halves that share a query
-    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-    return fmaxf(mx, __uint_as_float(hi ? sw[0] : sw[1]));
-  };
   float neg_m = INFINITY;                            // -m_run (log2 units, scaled)
   auto exp_pack = [&](f32x16 (&s)[2], const int st) {      // P = 2^(s c - m) of one 32-key half, packed; !MFMASUM: row sum
     float rs = 0.0f;
@@ -306,8 +264,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn8_kernel(const AttnParams p, c
   auto decide = [&](f32x16 (&s)[2], const int t) {
     // tail tile (wave-uniform, rare): invalid keys -> -inf (their K rows are clamped duplicates: finite scores)
     {
-      const int seg = (t < T0) ? 0 : 1;
-      const int nvalid = p.n[seg] - (seg ? (t - T0) : t) * KVT;
+      const KvTile kt = kv_tile(p, t, T0);
+      const int nvalid = kt.n - kt.kv0;
       if (nvalid < KVT) {
         // s[st][r] <-> key st*32 + 16 (r >> 3) + (r & 7) + 8 hi: compared against a limit that carries the lane half, from an
         // opaque copy of `hi` (else the 32 key indices are hoisted and live in registers across the hot loop)
@@ -328,7 +286,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn8_kernel(const AttnParams p, c
     }
     m0 = max3f(m0, m1, s[0][15]);
     m0 = max3f(m0, m0, s[1][15]);
-    const float mx = half_max(m0) * c;               // c > 0
+    const float mx = half_max(m0, hi) * c;               // c > 0
     if (__builtin_amdgcn_ballot_w64(mx > m_run + DEFER) != 0) {       // first tile: m_run = -inf -> always
       const float m_new = fmaxf(m_run, mx);
       const float al = __builtin_amdgcn_exp2f(m_run - m_new);          // exp2(-inf) = 0 on the first tile (O = l = 0 anyway)
@@ -404,44 +362,11 @@ __global__ __launch_bounds__(NW * 64, 2) void attn8_kernel(const AttnParams p, c
     }
   }
 
-  // ---- normalise and store.  o[mt][r]: e = mt*32 + (r&3) + 8*(r>>2) + 4*hi, q = l31.
-  float l_tot;
-  if constexpr (MFMASUM) {
-    constexpr int sel = (D & 31) >> 3;               // row D of O^T: tile D/32, register 4*sel of the hi = 0 lanes
-    l_tot = __shfl(o[NMT - 1][4 * sel], l31, 64);
-  } else {
-    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
-    l_tot = l_run + __uint_as_float(hi ? sw[0] : sw[1]);
-  }
-  const float inv = 1.0f / l_tot;
-  unsigned short* const ow = smem + wave * (32 * D);        // wave-private [32 queries][D] (the rings are dead: last barrier passed)
-  {
-    unsigned short* orow = ow + l31 * D;
-#pragma unroll
-    for (int mt = 0; mt < NMT; ++mt)
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int e = mt * 32 + 8 * qd + 4 * hi;
-        if (e < D) {
-          u32x2 pkd = {pack2<DT>(o[mt][4 * qd] * inv, o[mt][4 * qd + 1] * inv),
-                       pack2<DT>(o[mt][4 * qd + 2] * inv, o[mt][4 * qd + 3] * inv)};
-          *reinterpret_cast<u32x2*>(orow + e) = pkd;
-        }
-      }
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-  {
-    const int q0 = qb * (NW * 32) + wave * 32;
-    unsigned short* const obase = p.out + (size_t)b * p.sO + h * D;
-#pragma unroll
-    for (int j = 0; j < DCH / 2; ++j) {
-      const int c = lane + 64 * j;                    // 16-B chunk of the block, row-major
-      const int row = c / DCH, col = c - row * DCH;
-      const u32x4 v = *reinterpret_cast<const u32x4*>(ow + c * 8);
-      if (q0 + row < p.nq) *reinterpret_cast<u32x4*>(obase + (size_t)(q0 + row) * p.ldo + col * 8) = v;
-    }
-  }
+  // ---- normalise and store: the wave transposes its 32 x D block through its own slice of the (dead: last barrier passed) rings
+  const float l_tot = MFMASUM ? denominator_from_ones_row(o[NMT - 1], D, l31) : half_sum(l_run, hi);
+  unsigned short* const ow = smem + wave * (32 * D);
+  pack_o_rows<DT, NMT>(o, 1.0f / l_tot, D, hi, ow + l31 * D);
+  store_block16<32, DCH>(ow, p.out + (size_t)b * p.sO + h * D, p.ldo, qb * (NW * 32) + wave * 32, p.nq, lane);
 }
 
 template <int DT, int D, int NW, int MODE>
@@ -482,11 +407,7 @@ std::atomic<long long> idf_stat_attn8_launches{0};
 
 int g_attn8_mode = -2;
 int idf_attn8_mode() {
-  if (g_attn8_mode == -2) {
-    const char* e = getenv("IDF_ATTN8");
-    const int v = e ? atoi(e) : IDF_ATTN8_DEFAULT;
-    g_attn8_mode = (v < 0 || v > 6) ? IDF_ATTN8_DEFAULT : v;
-  }
+  if (g_attn8_mode == -2) g_attn8_mode = attn_mode_from_env("IDF_ATTN8", IDF_ATTN8_DEFAULT, 6);
   return g_attn8_mode;
 }
 int idf_attn8_set_mode(int v) { const int prev = idf_attn8_mode(); g_attn8_mode = v; return prev; }
@@ -495,15 +416,7 @@ int idf_launch_attn8(const AttnParams& p, int B, int dtype, hipStream_t s) {
   const int mode = idf_attn8_mode();
   if (mode == 0) return IDF_ATTN2_UNSUPPORTED;
   if (p.d != 80 && p.d != 160) return IDF_ATTN2_UNSUPPORTED;
-  if ((p.n[0] % 8) || (p.n[1] % 8)) return IDF_ATTN2_UNSUPPORTED;
-  if ((p.ldk[0] % 8) || (p.ldv[0] % 8) || (p.n[1] > 0 && ((p.ldk[1] % 8) || (p.ldv[1] % 8)))) return IDF_ATTN2_UNSUPPORTED;
-  if (!aligned16(p.k[0]) || !aligned16(p.vt[0]) || !aligned16(p.k[1]) || !aligned16(p.vt[1])) return IDF_ATTN2_UNSUPPORTED;
-  if ((p.sK[0] % 8) || (p.sV[0] % 8) || (p.sK[1] % 8) || (p.sV[1] % 8)) return IDF_ATTN2_UNSUPPORTED;
-  if (!aligned16(p.out) || (p.ldo % 8) || (p.sO % 8) || !aligned16(p.q) || (p.ldq % 8) || (p.sQ % 8)) return IDF_ATTN2_UNSUPPORTED;
-  // per-lane DMA offsets are 32-bit: a (batch, head) slice of K / V^T must stay below 2 GB
-  if ((long long)KVT * p.ldk[0] * 2 >= (1ll << 31) || (long long)p.d * p.ldv[0] * 2 >= (1ll << 31)) return IDF_ATTN2_UNSUPPORTED;
-  if (p.n[1] > 0 && ((long long)KVT * p.ldk[1] * 2 >= (1ll << 31) || (long long)p.d * p.ldv[1] * 2 >= (1ll << 31)))
-    return IDF_ATTN2_UNSUPPORTED;               // segment 1 goes through the same 32-bit offsets (as attention4.hip / attention4w.hip check)
+  if (!attn_dma_eligible(p, p.d)) return IDF_ATTN2_UNSUPPORTED;
   if (dtype == IDF_BF16) return launch_attn8<IDF_BF16>(p, B, mode, s);
   if (dtype == IDF_F16) return launch_attn8<IDF_F16>(p, B, mode, s);
   return IDF_ATTN2_UNSUPPORTED;

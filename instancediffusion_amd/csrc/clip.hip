@@ -302,14 +302,20 @@ __global__ __launch_bounds__(256) void clip_patchify_kernel(const float* __restr
   }
 }
 
+// the argument contract of idf_attention_causal / idf_attention_qkv (packed [B T][q | k | v] rows, d = 64, T <= tmax)
+int check_qkv_args(const void* qkv, int ld, const void* out, int ldo, int B, int T, int H, int d, float scale, int dtype, int tmax) {
+  if (!qkv || !out || B <= 0 || T <= 0 || H <= 0 || d <= 0 || !(scale > 0.0f)) return IDF_E_ARG;
+  if ((long long)ld < 3ll * H * d || (long long)ldo < (long long)H * d || (long long)B * H > 0x7fffffffll) return IDF_E_ARG;
+  if (d != 64 || T > tmax || (dtype != IDF_BF16 && dtype != IDF_F16)) return IDF_E_UNSUPPORTED;
+  if ((ld % 8) || (ldo % 8) || !aligned16(qkv) || !aligned16(out)) return IDF_E_ALIGN;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int idf_attention_causal(const void* qkv, int ld, void* out, int ldo, int B, int T, int H, int d, float scale, int dtype,
                                     void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || H <= 0 || d <= 0 || !(scale > 0.0f)) return IDF_E_ARG;
-  if ((long long)ld < 3ll * H * d || (long long)ldo < (long long)H * d || (long long)B * H > 0x7fffffffll) return IDF_E_ARG;
-  if (d != 64 || T > CA_TMAX || (dtype != IDF_BF16 && dtype != IDF_F16)) return IDF_E_UNSUPPORTED;
-  if ((ld % 8) || (ldo % 8) || !aligned16(qkv) || !aligned16(out)) return IDF_E_ALIGN;
+  if (const int e = check_qkv_args(qkv, ld, out, ldo, B, T, H, d, scale, dtype, CA_TMAX)) return e;
   hipStream_t s = (hipStream_t)stream;
   const float sl2 = scale * 1.4426950408889634f;
   const dim3 grid((unsigned)(B * H));
@@ -340,10 +346,7 @@ extern "C" int idf_clip_embed(const int* ids, const void* tok_emb, const void* p
 
 extern "C" int idf_attention_qkv(const void* qkv, int ld, void* out, int ldo, int B, int T, int H, int d, float scale, int dtype,
                                  void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || H <= 0 || d <= 0 || !(scale > 0.0f)) return IDF_E_ARG;
-  if ((long long)ld < 3ll * H * d || (long long)ldo < (long long)H * d || (long long)B * H > 0x7fffffffll) return IDF_E_ARG;
-  if (d != 64 || T > QA_TMAX || (dtype != IDF_BF16 && dtype != IDF_F16)) return IDF_E_UNSUPPORTED;
-  if ((ld % 8) || (ldo % 8) || !aligned16(qkv) || !aligned16(out)) return IDF_E_ALIGN;
+  if (const int e = check_qkv_args(qkv, ld, out, ldo, B, T, H, d, scale, dtype, QA_TMAX)) return e;
   hipStream_t s = (hipStream_t)stream;
   const float sl2 = scale * 1.4426950408889634f;
   const dim3 grid((unsigned)(B * H));

@@ -6,7 +6,8 @@ assembly with the library's flags and fails when either appears.      python too
 The row-resident kernels (mlp320w / qkv320w / qkv640w / geglu640w) depend on more than that: their generated streams wait with
 counted vmcnt / lgkmcnt, so the ORDER of every memory, LDS, MFMA and wait instruction the compiler emits around the streams is
 part of their correctness.  `skeleton()` extracts that order; to show that an edit of those files left it alone:
-    python tools/check_attn4w_isa.py --compare OLD_TREE NEW_TREE"""
+    python tools/check_attn4w_isa.py --compare OLD_TREE NEW_TREE [FILE:KERNEL ...]
+(without FILE:KERNEL pairs, e.g. attention8.hip:attn8_kernel, the row-resident kernels are compared)"""
 import collections
 import os
 import re
@@ -39,8 +40,8 @@ def bodies(txt, kernel):
 
 
 def skeleton(src, kernel, extra=()):
-    """per instantiation `kernel<DT>`: seq = the ordered memory / LDS / MFMA / AGPR mnemonics and every s_waitcnt WITH its
-    operands; mnemonics = the multiset of all instructions; desc = the kernel descriptor's register and segment sizes"""
+    """per instantiation (keyed by its mangled name): seq = the ordered memory / LDS / MFMA / AGPR mnemonics and every s_waitcnt
+    WITH its operands; mnemonics = the multiset of all instructions; desc = the kernel descriptor's register and segment sizes"""
     txt = listing(src, extra)
     out = {}
     for name, body in bodies(txt, kernel):
@@ -57,15 +58,15 @@ def skeleton(src, kernel, extra=()):
                 seq.append(m)
         blk = re.search(r"\.amdhsa_kernel " + re.escape(name) + r"\n(.*?)\.end_amdhsa_kernel", txt, flags=re.S).group(1)
         desc = {k: int(re.search(r"\.amdhsa_" + k + r" (\d+)", blk).group(1)) for k in DESCRIPTOR}
-        out[kernel + "<" + re.search(r"ILi(\d+)E", name).group(1) + ">"] = dict(seq=seq, mnemonics=mnem, desc=desc)
+        out[name] = dict(seq=seq, mnemonics=mnem, desc=desc)
     return out
 
 
-def compare(old_tree, new_tree):
-    """0 when every row kernel of new_tree has the ordered sequence and the descriptor of old_tree's; prints the instructions
-    added / removed where the mnemonic multisets differ (address arithmetic may; nothing else should)"""
+def compare(old_tree, new_tree, kernels=ROW_KERNELS):
+    """0 when every kernel of `kernels` [(file, kernel)] in new_tree has the ordered sequence and the descriptor of old_tree's;
+    prints the instructions added / removed where the mnemonic multisets differ (address arithmetic may; nothing else should)"""
     bad = False
-    for f, kernel in ROW_KERNELS:
+    for f, kernel in kernels:
         a, b = (skeleton(os.path.join(t, "instancediffusion_amd", "csrc", f), kernel) for t in (old_tree, new_tree))
         bad |= sorted(a) != sorted(b) or not a
         for k in sorted(set(a) & set(b)):
@@ -101,7 +102,8 @@ def check(extra=(), src=SRC, kernel="attn4w_kernel"):
 
 if __name__ == "__main__":
     if sys.argv[1:2] == ["--compare"]:
-        sys.exit(compare(os.path.abspath(sys.argv[2]), os.path.abspath(sys.argv[3])))
+        pairs = [tuple(a.split(":", 1)) for a in sys.argv[4:]] or ROW_KERNELS
+        sys.exit(compare(os.path.abspath(sys.argv[2]), os.path.abspath(sys.argv[3]), pairs))
     rep = check(sys.argv[1:])
     bad = False
     for k, v in rep.items():
