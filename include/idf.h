@@ -127,7 +127,9 @@ enum { IDF_STAT_GEMM_BIG_LAUNCHES = 0, IDF_STAT_ATTN2_LAUNCHES = 1, IDF_STAT_GEM
                                       (0 = IDF_TUNE_PROJ_ROW or IDF_TUNE_GEMM_BIG is 0), so a caller can plan who produces ln_stats */,
        IDF_STAT_ATTN_RES_LAUNCHES = 10 /* idf_attention calls served by the resident-key form of the 32-query kernel (<= 2 key tiles staged
                                           once per workgroup, which walks several query blocks); a new enum value within ABI 5, as knob 9 was;
-                                          stat id 5 stays unassigned */ };
+                                          stat id 5 stays unassigned */,
+       IDF_STAT_CLIP_PREPROC_LAUNCHES = 12 /* idf_clip_crop_resize launches; a new enum value within ABI 5; id 11 stays unassigned -- it is
+                                              the id the C-ABI tests probe as the first unknown counter, idf_get_stat(11) == -1 */ };
 long long idf_get_stat(int stat);
 
 /* ---- GEMM: out[M,N] = epi( A[M,K] . W[N,K]^T ) ----------------------------------------------------------
@@ -391,6 +393,33 @@ int idf_clip_embed(const int* ids, const void* tok_emb, const void* pos_emb, voi
 int idf_attention_qkv(const void* qkv, int ld, void* out, int ldo, int B, int T, int H, int d, float scale, int dtype, void* stream);
 int idf_clip_patchify(const float* pixels, void* patches, int ldp, const void* cls_row, void* x, int ldx, int B, int S, int P, int C,
                       int dtype, void* stream);
+
+/* ---- CLIP preprocessing on the device (host/clip_score.py: crop_instances + preprocess; eval/eval_attribute_binding.py:186-190 and
+ * the CLIPFeatureExtractor behind it).  Added within ABI 5: a new symbol and new enum values only.
+ * idf_clip_crop_resize: one launch turns a batch of source images and a list of crops into the image tower's input,
+ *   out fp32 [Ncrop][3][S][S] = (v / 255 - mean) / std of the crop, bicubic-resized so that its short side is S and centre-cropped to
+ *   S x S, BIT FOR BIT what Pillow's Image.resize(BICUBIC) gives: its 8-bit resample is two integer passes,
+ *   clip8((2^21 + sum pixel * k) >> 22) in int32, horizontal then vertical on the uint8 result, over coefficient tables that the
+ *   HOST builds in float64 (host/clip_score.resample_tables) -- the kernel evaluates no filter and no fp32 expression that could round.
+ * src, by `kind`: IDF_CLIP_SRC_U8 uint8 [B][H][W][3] (what a PNG holds), or IDF_CLIP_SRC_F32 fp32 [B][3][H][W] (what
+ *   AutoencoderKL.decode returns; finite values), quantised on the way in as inference.save_images does: clamp to [-1, 1],
+ *   * 0.5 + 0.5, * 255 in fp32, truncation.
+ * crops: HOST memory, int32 [Ncrop][8] = (image b, x0, y0, width, height, table set t, 0, 0), the rectangle inside the image; checked
+ *   here, before any launch.
+ * tables: DEVICE memory, int32, three blocks: the same Ncrop crop records; then per table set [2 axes][S][2] = (first, count) of every
+ *   output index of the S-wide window (axis 0 horizontal, 1 vertical; first counts from the crop's corner); then per table set
+ *   [2 axes][K][S] coefficients, tap-major, zero behind an index' count.  Crops of one size share a table set (Ntab <= Ncrop).
+ *   K = the largest Pillow ksize of the call, 2 ceil(support) + 1 (11 for 512 -> 224).
+ * lut: DEVICE fp32 [3][256], channel c / byte v -> output value (host/clip_score.pixel_lut).
+ * IDF_E_ARG: a null pointer, B / H / W / Ncrop / Ntab / S / K < 1, S % 4, Ncrop > 65535, an unknown kind, a crop record outside its
+ *   image or table range; IDF_E_UNSUPPORTED: K > IDF_CLIP_RESIZE_KMAX = 32 (a 1024-px short side resized to 224 needs 21), or an S
+ *   whose band of intermediate rows does not fit the kernel's 48 KB of LDS at K taps; IDF_E_ALIGN: out not 16-B aligned, tables /
+ *   lut / fp32 src not 4-B aligned.  All before any launch (IDF_STAT_CLIP_PREPROC_LAUNCHES counts the launches).  Device table
+ *   entries are clamped wherever they become an address. */
+enum { IDF_CLIP_SRC_U8 = 0, IDF_CLIP_SRC_F32 = 1 };
+#define IDF_CLIP_RESIZE_KMAX 32
+int idf_clip_crop_resize(const void* src, int kind, int B, int H, int W, const int* crops, int Ncrop, const int* tables, int Ntab,
+                         const float* lut, float* out, int S, int K, void* stream);
 
 /* ---- layout helpers ---------------------------------------------------------------------------------------*/
 int idf_cast_f32_to_16(const float* x, void* out, long long n, int dtype, void* stream);

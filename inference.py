@@ -89,6 +89,24 @@ def save_images(images: torch.Tensor, folder: str) -> list:
     return names
 
 
+def clip_scores(args, images: torch.Tensor, data: dict, dtype) -> dict:
+    """``--clip_score``: the local CLIP score (host/clip_score.py) of every instance of every decoded image, straight from the fp32
+    decoder output -- on backend ``hip`` the pixels never leave the device (``idf_clip_crop_resize`` quantises them as
+    ``save_images`` does).  -> the content of ``clip_scores.json``."""
+    from instancediffusion_amd.host import clip_score as cs
+    boxes, phrases = cs.instances_from_demo_json(data)
+    model, tokenize, tokenizer = cs.load_clip(args.clip_path)
+    scorer = cs.InstanceClipScorer(model.to(images.device), tokenize, backend=args.clip_score, dtype=dtype)
+    scores = scorer.score_batch(images.float(), boxes, phrases)
+    means, ranking = cs.rank_by_mean(scores)
+    return dict(metric="local CLIP score (eval_attribute_binding.py, HF branch)", input_json=args.input_json, backend=args.clip_score,
+                dtype=args.dtype if args.clip_score == "hip" else "fp32", tokenizer=tokenizer,
+                weights=args.clip_path or "synthetic", phrases=phrases,
+                images={str(i): [round(v, 6) for v in s] for i, s in enumerate(scores)},
+                means={str(i): round(m, 6) for i, m in enumerate(means)}, ranking=ranking,
+                mean=round(sum(means) / len(means), 6))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--output", type=str, default="OUTPUT")
@@ -113,7 +131,19 @@ def main():
     ap.add_argument("--save_latents", action="store_true")
     ap.add_argument("--use_masked_att", action="store_true",
                     help="masked gated self-attention (attention.py:187-255): instance patches only see their own box")
+    ap.add_argument("--clip_score", choices=["hf", "hip"], default=None,
+                    help="score every instance crop of every image against its phrase (local CLIP score) and write clip_scores.json "
+                         "next to the PNGs; hip: crop, resize and both CLIP towers on the HIP kernels, from the decoder output on the device")
+    ap.add_argument("--clip_path", type=str, default=None,
+                    help="--clip_score: local directory of openai/clip-vit-large-patch14 (local files only); with --synthetic_weights "
+                         "and no path, a key-seeded synthetic CLIP model")
+    ap.add_argument("--keep_best", type=int, default=None,
+                    help="write only the K images with the best mean CLIP score (needs --clip_score; the JSON still lists all)")
     args = ap.parse_args()
+    if args.keep_best is not None and (args.clip_score is None or args.keep_best < 1):
+        raise SystemExit("--keep_best K needs --clip_score and K >= 1")
+    if args.clip_score and not (args.clip_path or args.synthetic_weights):
+        raise SystemExit("--clip_score needs --clip_path DIR (or --synthetic_weights for the synthetic CLIP model)")
     if args.cascade_strength > 0:
         raise SystemExit("the SDXL refiner cascade is outside the sampling path (needs diffusers + downloads)")
     dev = torch.device(args.device)
@@ -177,7 +207,17 @@ def main():
         samples = sampler.sample(S=args.steps, shape=shape, input=inp, uc=uc, guidance_scale=args.guidance_scale)
     images = autoencoder.decode(samples)                                   # inference.py:95
     folder = os.path.join(args.output, save_folder_name)
+    report = None
+    if args.clip_score:
+        report = clip_scores(args, images, data, dtype)
+        if args.keep_best is not None:                                     # best first; the JSON still lists every image
+            images = images[report["ranking"][:args.keep_best]]
     names = save_images(images, folder)
+    if report is not None:
+        kept = report["ranking"][:args.keep_best] if args.keep_best is not None else list(range(len(names)))
+        report["saved"] = {os.path.basename(n): i for n, i in zip(names, kept)}
+        with open(os.path.join(folder, "clip_scores.json"), "w") as f:
+            f.write(json.dumps(report, indent=1) + "\n")
     if args.save_latents:
         torch.save(dict(latents=samples.cpu(), caption=data["caption"], phrases=meta["phrases"]),
                    os.path.join(folder, "latents.pt"))

@@ -16,6 +16,9 @@ IDF_STAT_GEMM_BIG_LAUNCHES, IDF_STAT_ATTN2_LAUNCHES, IDF_STAT_GEMM_RING_LAUNCHES
 IDF_STAT_QKV_ROW_LAUNCHES, IDF_STAT_GEGLU_ROW_LAUNCHES = 6, 7
 IDF_STAT_PROJ_ROW_LAUNCHES, IDF_STAT_PROJ_ROW_MIN_M = 8, 9
 IDF_STAT_ATTN_RES_LAUNCHES = 10  # launches served by the resident-key form of the 32-query attention kernel
+IDF_STAT_CLIP_PREPROC_LAUNCHES = 12  # idf_clip_crop_resize launches (11 is unassigned: the tests' first unknown id)
+IDF_CLIP_SRC_U8, IDF_CLIP_SRC_F32 = 0, 1  # idf_clip_crop_resize source kinds
+CLIP_RESIZE_KMAX = 32                # IDF_CLIP_RESIZE_KMAX
 IDF_TUNE_PROJ_ROW = 9            # (8 is unassigned: idf_set_tuning(8, ..) is IDF_E_ARG)
 IDF_TUNE_GEMM_BIG, IDF_TUNE_ATTN2, IDF_TUNE_GEMM_RING, IDF_TUNE_BIG_MIN_EFF, IDF_TUNE_ATTN8, IDF_TUNE_MLP, IDF_TUNE_QKV_ROW, IDF_TUNE_GEGLU_ROW = 0, 1, 2, 3, 4, 5, 6, 7      # idf_set_tuning
 EPI_LN_ROW, EPI_LN_COL, EPI_GEGLU_P32, EPI_QUICKGELU = 512, 1024, 2048, 4096
@@ -100,6 +103,7 @@ SYMBOLS = {
     "idf_clip_embed": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
     "idf_attention_qkv": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, cf, ci, vp]),
     "idf_clip_patchify": (ci, [vp, vp, ci, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
+    "idf_clip_crop_resize": (ci, [vp, ci, ci, ci, ci, vp, ci, vp, ci, vp, vp, ci, ci, vp]),
 }
 
 _lib = None

@@ -15,6 +15,7 @@
 #include "gemm_core.h"
 #include "attn_core.h"
 #include <cstdlib>
+extern std::atomic<long long> idf_stat_clip_preproc_launches;   // clip_preproc.hip: idf_clip_crop_resize launches (idf_get_stat)
 
 using namespace idfcore;
 
@@ -982,6 +983,7 @@ extern "C" long long idf_get_stat(int stat) {
   if (stat == IDF_STAT_PROJ_ROW_LAUNCHES) return idf_stat_projw_launches.load();
   if (stat == IDF_STAT_PROJ_ROW_MIN_M) return gemm_big_mode() > 0 ? idf_projw_min_rows() : 0;
   if (stat == IDF_STAT_ATTN_RES_LAUNCHES) return idf_stat_attn_res_launches.load();
+  if (stat == IDF_STAT_CLIP_PREPROC_LAUNCHES) return idf_stat_clip_preproc_launches.load();
   return -1;
 }
 

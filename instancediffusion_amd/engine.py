@@ -14,6 +14,8 @@ MI355X-first design decisions (vs the reference's PyTorch module tree):
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -21,6 +23,24 @@ import torch
 
 from .host.attention import SpatialTransformer
 from .host.unet import Downsample, ResBlock, UNetModel, Upsample
+
+
+@contextlib.contextmanager
+def capture_graph(graph):
+    """``torch.cuda.graph(graph)`` with the cyclic garbage collector held off.  torch.cuda.graph no longer collects on entry, so a
+    dead cycle from earlier work (a dropped model with its engine, graphs and events) could be finalised between two captured
+    launches, and a finaliser that calls the runtime inside a capture aborts the process (seen in the GPU suite: ``Fatal Python
+    error: Aborted`` while garbage-collecting inside the capture of a sampler test).  Collect before, keep the collector out."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph):
+            yield
+    finally:
+        if was_on:
+            gc.enable()
+
 
 # LayerNorm statistics of the folded GEMMs (A/B switch, env IDF_LN_SELF): 0 = every producer of the residual stream emits them
 # (out_stats pass), 2 = every LN_ROW consumer sums its own A rows, 1 (default) = q/k and cross-q sum their own, the GEGLU GEMMs
@@ -913,7 +933,7 @@ class UNetEngine:
                 self._forward_ops(x_s, t_s, slot, eps_s, fuser_on, paired)
                 torch.cuda.synchronize()
                 graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
+                with capture_graph(graph):
                     self._forward_ops(x_s, t_s, slot, eps_s, fuser_on, paired)
                 self._graphs[key] = graph
             graph.replay()

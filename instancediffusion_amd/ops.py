@@ -373,6 +373,28 @@ class HipOps:
                                               Cc, self.dt, self._stream()), "idf_clip_patchify")
         return patch
 
+    CLIP_RESIZE_KMAX = _lib.CLIP_RESIZE_KMAX
+
+    def clip_crop_resize(self, src, crops, tables, ntab, lut, out, K):
+        """``idf_clip_crop_resize``: src uint8 [B, H, W, 3] or fp32 [B, 3, H, W] contiguous on the device; crops int32 numpy
+        [Ncrop, 8] on the HOST (image, x0, y0, width, height, table set, 0, 0); tables int32 on the device (the packed blob of
+        ``host.clip_score.pack_crop_tables``: crop records, bounds, tap-major coefficients of ``ntab`` table sets at K taps);
+        lut fp32 [3, 256]; out fp32 [Ncrop, 3, S, S] contiguous.  Bit-identical to Pillow's crop + bicubic resize + CLIP normalisation."""
+        import numpy as np
+        if src.dtype == torch.uint8:
+            kind, (B, H, W, ch) = _lib.IDF_CLIP_SRC_U8, src.shape
+        else:
+            kind, (B, ch, H, W) = _lib.IDF_CLIP_SRC_F32, src.shape
+            assert src.dtype == torch.float32
+        Ncrop, S = out.shape[0], out.shape[-1]
+        assert ch == 3 and src.is_contiguous() and src.is_cuda and out.is_contiguous() and out.dtype == torch.float32
+        assert tuple(out.shape) == (Ncrop, 3, S, S) and lut.dtype == torch.float32 and tuple(lut.shape) == (3, 256) and lut.is_contiguous()
+        assert isinstance(crops, np.ndarray) and crops.dtype == np.int32 and crops.shape == (Ncrop, 8) and crops.flags.c_contiguous
+        assert tables.dtype == torch.int32 and tables.is_contiguous() and tables.numel() >= Ncrop * 8 + ntab * (4 * S + 2 * K * S)
+        _lib.check(self.lib.idf_clip_crop_resize(_p(src), kind, B, H, W, C.c_void_p(crops.ctypes.data), Ncrop, _p(tables), int(ntab),
+                                                 _p(lut), _p(out), S, int(K), self._stream()), "idf_clip_crop_resize")
+        return out
+
     def groupnorm(self, x, out, gamma, beta, eps, silu, partial=None):
         """x/out [B, HW, C] (or [B,H,W,C]) contiguous.  ``partial``: the statistics of x are already there ([B, nchunks, 32, 2]
         fp32 (mean, M2) per row chunk, as a conv3x3 leaves them): only the normalise pass runs."""

@@ -25,7 +25,7 @@ from typing import Dict
 
 import torch
 
-from .engine import _Lin, pack_conv3x3
+from .engine import _Lin, capture_graph, pack_conv3x3
 
 
 class _VAEEngine:
@@ -153,7 +153,7 @@ class _VAEEngine:
             enqueue()                                  # eager warm-up sizes every buffer
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            with capture_graph(graph):
                 enqueue()
             self._graphs[key] = graph
         graph.replay()

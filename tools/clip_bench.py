@@ -4,10 +4,13 @@ against the Hugging Face ``CLIPTextModel`` it replaces (PyTorch eager) in the sa
 
     python tools/clip_bench.py [--iters 7] [--dtype bf16|fp16] [--out profiles/clip_encode_bench.json]
     python tools/clip_bench.py --vision [--iters 7] [--dtype bf16|fp16] [--sizes 8 256] [--out profiles/clip_vision_bench.json]
+    python tools/clip_bench.py --score [--iters 7] [--dtype bf16|fp16] [--out profiles/clip_score_batched.json]
 
 ``--vision`` times the ViT-L/14 image tower instead (``CLIPVisionEngine`` against ``CLIPVisionModelWithProjection``) at B = 8 and
 B = 256 crops (8 instances x 32 images) of 224 x 224, T = 257, with the same method, and adds the GEMM / attention / rest split of
-one engine pass.  Run it under ``timeout`` as every GPU step.
+one engine pass.  ``--score`` times the local CLIP score of 32 images x 8 instances: the per-image ``score()`` loop against
+``score_batch`` from a device-resident fp32 batch, the crop kernel alone (bytes, GB/s) and the PIL preprocessing alone.  Run it under
+``timeout`` as every GPU step.
 
 Sizes: B = 2 sequences (prompt + negative prompt) and B = 288 (the per-instance prompts of the Multi-instance Sampler at N = 8 and
 32 images), T = 77.  The three paths alternate inside one process, each timed ``iters`` (>= 5) times after a warm-up; the figure
@@ -113,20 +116,84 @@ def main_vision(args, iters, dtype):
     return res
 
 
+def main_score(args, iters, dtype):
+    """``--score``: 32 images of 512 x 512, 8 instances (the four boxes of demos/demo_four_boxes.json and their mirror images),
+    synthetic ViT-L/14 weights: the per-image ``InstanceClipScorer.score`` loop (PIL crop + resize on the host, the tower on 8 crops
+    at a time, one text call per phrase per image) against ``score_batch`` on the fp32 batch as it lies on the device after
+    ``AutoencoderKL.decode``; beside them the crop kernel alone and the PIL preprocessing of the same crops alone."""
+    import numpy as np
+    from PIL import Image
+    from instancediffusion_amd.host import clip_score as cs
+    B, HW = 32, 512
+    data = json.load(open(os.path.join(REPO, "demos", "demo_four_boxes.json")))
+    boxes, phrases = cs.instances_from_demo_json(data)
+    boxes = boxes + [[1.0 - b[2], b[1], 1.0 - b[0], b[3]] for b in boxes]
+    phrases = phrases + ["the mirror image of " + p for p in phrases]
+    model, tokenize, tokenizer = cs.load_clip(None)
+    scorer = cs.InstanceClipScorer(model.cuda(), tokenize, backend="hip", dtype=dtype)
+    g = torch.Generator().manual_seed(0)
+    batch = (torch.rand((B, 3, HW, HW), generator=g) * 2.4 - 1.2).cuda()                 # decoder output, some of it beyond [-1, 1]
+    pil = [Image.fromarray(a) for a in cs.quantise_images(batch)]
+    S = scorer.size
+    rects = cs.crop_rects(boxes, HW, HW)
+    crops, blob, ntab, K = cs.pack_crop_tables(rects * B, [b for b in range(B) for _ in rects], S)
+    tables, lut = torch.from_numpy(blob).cuda(), cs.pixel_lut().cuda()
+    out = torch.empty((B * len(rects), 3, S, S), dtype=torch.float32, device="cuda")
+    ops = scorer._vision.ops
+    bytes_read = sum(3 * 4 * (x1 - x0) * (y1 - y0) for x0, y0, x1, y1 in rects) * B + blob.nbytes
+    bytes_written = out.numel() * 4
+    paths = {"score_loop": lambda: [scorer.score(im, boxes, phrases) for im in pil],
+             "score_batch": lambda: scorer.score_batch(batch, boxes, phrases),
+             "crop_kernel": lambda: ops.clip_crop_resize(batch, crops, tables, ntab, lut, out, K),
+             "pil_preprocess": lambda: [cs.preprocess(c, S) for im in pil for c in cs.crop_instances(im, boxes)]}
+    with torch.no_grad():
+        loop, batched = paths["score_loop"](), paths["score_batch"]()                    # warm-up: buffers, kernel selection, caches
+        for fn in paths.values():
+            fn()
+        times = {k: [] for k in paths}
+        for _ in range(iters):                               # alternately, so that all see the same clocks
+            for k, fn in paths.items():
+                times[k].append(timed_ms(fn))
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        dev_ms = []
+        for _ in range(iters):                               # the kernel on the device alone: HIP events around 20 launches
+            s.record()
+            for _ in range(20):
+                paths["crop_kernel"]()
+            e.record()
+            torch.cuda.synchronize()
+            dev_ms.append(s.elapsed_time(e) / 20)
+    entry = {k: dict(median_ms=round(statistics.median(v), 3), min_ms=round(min(v), 3), max_ms=round(max(v), 3)) for k, v in times.items()}
+    kern_ms = statistics.median(dev_ms)
+    diff = max(abs(a - b) for x, y in zip(loop, batched) for a, b in zip(x, y))
+    return dict(what="local CLIP score of 32 images of 512 x 512, 8 instances each, ViT-L/14 synthetic weights: per-image score() loop "
+                     "vs score_batch from the device-resident fp32 batch, ms per call (median of alternated runs)",
+                dtype=args.dtype, iters=iters, device=torch.cuda.get_device_name(0), images=B, instances=len(rects), taps=K,
+                table_sets=ntab, **entry,
+                speedup_batch_vs_loop=round(entry["score_loop"]["median_ms"] / entry["score_batch"]["median_ms"], 2),
+                batch_faster_beyond_spread=bool(entry["score_batch"]["max_ms"] < entry["score_loop"]["min_ms"]),
+                crop_kernel_device=dict(median_ms=round(kern_ms, 4), min_ms=round(min(dev_ms), 4), max_ms=round(max(dev_ms), 4),
+                                        bytes_read=int(bytes_read), bytes_written=int(bytes_written),
+                                        gb_per_s=round((bytes_read + bytes_written) / kern_ms / 1e6, 1)),
+                max_abs_score_difference_loop_vs_batch=diff)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=7)
     ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16")
     ap.add_argument("--sizes", type=int, nargs="+", default=None)
     ap.add_argument("--vision", action="store_true", help="time the image tower (CLIPVisionEngine) instead of the text transformer")
+    ap.add_argument("--score", action="store_true", help="time the local CLIP score: the per-image score() loop against score_batch")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     iters = max(args.iters, 5)
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "clip_vision_bench.json" if args.vision else "clip_encode_bench.json")
-    if args.vision:
-        res = main_vision(args, iters, dtype)
+        args.out = os.path.join(REPO, "profiles", "clip_score_batched.json" if args.score else
+                                "clip_vision_bench.json" if args.vision else "clip_encode_bench.json")
+    if args.vision or args.score:
+        res = (main_score if args.score else main_vision)(args, iters, dtype)
         print(json.dumps(res))
         if args.out:
             with open(args.out, "w") as f:
