@@ -37,7 +37,7 @@ using namespace idfattn;
 
 namespace {
 
-IDF_ATTN_ZERO_PAGE(idf_attn4_zero_page);
+IDF_ZERO_PAGE(idf_attn4_zero_page);
 IDF_ATTN_ONES_PAGE(idf_attn4_ones_page);
 
 struct TrueT { static constexpr bool value = true; };

@@ -30,7 +30,7 @@ using namespace idfattn;
 
 namespace {
 
-IDF_ATTN_ZERO_PAGE(idf_attn4w_zero_page);
+IDF_ZERO_PAGE(idf_attn4w_zero_page);
 IDF_ATTN_ONES_PAGE(idf_attn4w_ones_page);
 
 constexpr int D = 40, DCH = 5, NKS = 3, NMT = 2;

@@ -35,7 +35,7 @@ using namespace idfattn;
 
 namespace {
 
-IDF_ATTN_ZERO_PAGE(idf_attn8_zero_page);
+IDF_ZERO_PAGE(idf_attn8_zero_page);
 
 constexpr float DEFER = 6.0f;                        // log2 units a tile maximum may exceed the reference without a rescale
 

@@ -28,36 +28,12 @@ struct AttnParams {
 // ================================================================================================================
 constexpr int KVT = 64;            // keys per tile, in every kernel of the family
 
-// The 128-B zero page (source of the V^T chunks beyond n) and the bf16 / fp16 ones page (source of the softmax-denominator row)
-// of an LDS-DMA kernel.  Device globals cannot be shared between translation units built with -fno-gpu-rdc, so every file that
-// needs one defines its own through these.
-#define IDF_ATTN_ZERO_PAGE(name) __device__ __attribute__((aligned(128))) unsigned short name[64]
+// The bf16 / fp16 ones page (source of the softmax-denominator row) of an LDS-DMA kernel; like the zero page (IDF_ZERO_PAGE,
+// common.h, next to the LDS-DMA primitives) every file that needs one defines its own through this.
 #define IDF_ATTN_ONES_PAGE(name)                                                                        \
   __device__ __attribute__((aligned(16))) unsigned short name[2][8] = {                                 \
       {0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80},      /* bf16 1.0 */            \
       {0x3c00, 0x3c00, 0x3c00, 0x3c00, 0x3c00, 0x3c00, 0x3c00, 0x3c00}}      /* fp16 1.0 */
-
-// ---- LDS-DMA (global_load_lds_dwordx4) issued through inline asm: the compiler's waitcnt pass otherwise puts s_waitcnt vmcnt(0)
-// in front of the first ds_read that follows ANY pending global_load_lds (it cannot tell the ring stages apart), which would
-// serialise the prefetch with the tile's own LDS reads.  Ordering is the kernel's: `s_waitcnt vmcnt(..)` + s_barrier at the end of
-// every tile.  lds = LDS byte address of lane 0's 16-B slot (lane i lands at lds + 16 i); it is wave-uniform by construction,
-// readfirstlane makes it provably so, and it goes through M0.  M0 cannot be declared in the clobber list (hipcc: "reserved
-// register"); it is ours in these kernels -- nothing else in them uses it (no movrel / GWS / sendmsg, no LDS-DMA builtin) and
-// every asm statement that reads it writes it first.
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)p; }
-__device__ __forceinline__ void dma16_sv(const void* sbase /* wave-uniform */, unsigned voff, unsigned lds) {
-  lds = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(voff), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ void dma16_v(const void* addr /* per lane */, unsigned lds) {
-  lds = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds), "v"(addr) : "memory");
-}
-__device__ __forceinline__ const void* uniform_ptr(const void* p) {      // provably wave-uniform (an SGPR pair for the asm operand)
-  const unsigned long long a = (unsigned long long)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-  return (const void*)(((unsigned long long)hi << 32) | lo);
-}
 
 __device__ __forceinline__ float max3f(float a, float b, float c) {
   float r;

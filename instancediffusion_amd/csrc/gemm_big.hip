@@ -42,7 +42,7 @@ using namespace idfcore;
 
 namespace {
 
-__device__ __attribute__((aligned(128))) unsigned short idf_zero_page[64];   // zero-initialised device memory
+IDF_ZERO_PAGE(idf_zero_page);
 
 // Wave tile: IDF_WAVE_ROWS rows x BN/2 columns.  64 (library): eight waves per workgroup, two per SIMD, 160 accumulator
 // registers per lane.  128 (experiment of tools/ubench/big_trace.hip, see profiles/DESIGN_r01_r05_full.md "What bounds the GEMM family"): four waves,
@@ -56,22 +56,6 @@ constexpr int NWAVES = 2 * 256 / WM;          // waves per 256-row workgroup til
 template <int I> struct IC { static constexpr int value = I; };
 template <int I, int N, int STEP, class F> __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (I < N) { f(IC<I>{}); static_for<I + STEP, N, STEP>(f); }
-}
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// LDS-DMA as inline assembly: with the builtin the compiler orders every later ds_read behind ALL outstanding LDS-DMA
-// (s_waitcnt vmcnt(0)); both kernels below keep LDS-DMA in flight across their fragment reads and do their own waits.  lds = LDS byte address of lane 0's 16-B slot (lane i lands at lds + 16 i); it goes through M0, which
-// nothing else in that kernel uses.
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)p; }
-__device__ __forceinline__ void dma16_sv(const void* sbase /* wave-uniform */, unsigned voff_bytes, unsigned lds) {
-  lds = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(voff_bytes), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ void dma16_v(const void* addr /* per lane */, unsigned lds) {
-  lds = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds), "v"(addr) : "memory");
 }
 
 // ---------------- tile epilogue (shared by the lock-step and the ping-pong kernel): no LDS, no barrier.
@@ -134,6 +118,17 @@ __device__ __forceinline__ void gst_scatter_step(float* t, int l31) {
     t[i] = keep + __shfl_xor(send, H, 64);
   }
 }
+// the two v_permlane32_swap per register pair of the epilogues: c = one 32 x 32 accumulator fragment -> v = the lane's 16
+// consecutive columns of its row
+__device__ __forceinline__ void swap16(const f32x16& c, float* v) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const auto s02 = __builtin_amdgcn_permlane32_swap(__float_as_uint(c[e]), __float_as_uint(c[8 + e]), false, false);
+    const auto s13 = __builtin_amdgcn_permlane32_swap(__float_as_uint(c[4 + e]), __float_as_uint(c[12 + e]), false, false);
+    v[e] = __uint_as_float(s02[0]); v[4 + e] = __uint_as_float(s02[1]);
+    v[8 + e] = __uint_as_float(s13[0]); v[12 + e] = __uint_as_float(s13[1]);
+  }
+}
 template <int DT, int BM, int BN, int TN, bool SPLIT, bool LNS = false, bool STATS = false, bool GLU = false, bool GST = false,
           bool QG = true /* IDF_EPI_QUICKGELU compiled in: the dense GEMMs; no conv carries the flag */>
 __device__ __forceinline__ void big_epilogue(const CoreParams& p, f32x16 (&acc)[TN][TM], int seq, int slice, int tiles_n, int wm,
@@ -161,15 +156,6 @@ __device__ __forceinline__ void big_epilogue(const CoreParams& p, f32x16 (&acc)[
   const int m_tile = seq / tiles_n;
   const int n0 = (seq - m_tile * tiles_n) * BN, m0 = m_tile * BM;
   const int mw = m0 + wm * WM, nw = n0 + wn * WN;
-  auto swap16 = [&](const f32x16& c, float* v) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const auto s02 = __builtin_amdgcn_permlane32_swap(__float_as_uint(c[e]), __float_as_uint(c[8 + e]), false, false);
-      const auto s13 = __builtin_amdgcn_permlane32_swap(__float_as_uint(c[4 + e]), __float_as_uint(c[12 + e]), false, false);
-      v[e] = __uint_as_float(s02[0]); v[4 + e] = __uint_as_float(s02[1]);
-      v[8 + e] = __uint_as_float(s13[0]); v[12 + e] = __uint_as_float(s13[1]);
-    }
-  };
   if constexpr (LNS) {                                      // leave the row statistics for an LN_COL consumer of A
     if (p.ln_stats_out && n0 == 0 && wn == 0 && hi == 0) {
 #pragma unroll
@@ -605,13 +591,7 @@ __device__ __forceinline__ void big_epilogue_fold(const CoreParams& p, f32x16 (&
 #pragma unroll
     for (int b = 0; b < TM; ++b) {
       float v[16];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const auto s02 = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[a][b][e]), __float_as_uint(acc[a][b][8 + e]), false, false);
-        const auto s13 = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[a][b][4 + e]), __float_as_uint(acc[a][b][12 + e]), false, false);
-        v[e] = __uint_as_float(s02[0]); v[4 + e] = __uint_as_float(s02[1]);
-        v[8 + e] = __uint_as_float(s13[0]); v[12 + e] = __uint_as_float(s13[1]);
-      }
+      swap16(acc[a][b], v);
       if (p.epi & IDF_EPI_BIAS) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) v[j] += bs[j >> 2][j & 3];
@@ -722,9 +702,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
       const int m = min(m0 + row, p.M - 1);
       const unsigned sw = (unsigned)((dc ^ swz(row)) * 8);
       if (CONV) {
-        const int hw = p.Ho * p.Wo;
-        const int b = m / hw, rem = m - b * hw;
-        const int yo = rem / p.Wo, xo = rem - yo * p.Wo;
+        const auto [b, yo, xo] = conv_pixel(p, m);
         if constexpr (FOLD) {
           // 2x2 window on the low-resolution image: output row 2 yo + py reads source rows yo - 1 + py and yo + py (columns
           // likewise), and the zero padding of the upsampled image is the zero padding of this one -- a 4-bit mask
@@ -761,7 +739,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
         aoff[j] = (unsigned)m * (unsigned)p.lda + sw;
       }
     }
-    if (CONV) { const int k_elem = l_k0 * BKT; tap = k_elem / p.Cin; ci0 = k_elem - tap * p.Cin; }
+    if (CONV) conv_tap_at(p, l_k0 * BKT, tap, ci0);
   };
 
   // LDS-DMA pieces of the K-tile the loader stands on: piece i < W_INST = weight rows, else activation rows.  Inline
@@ -791,7 +769,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
         const int ky = tap / 3, kx = tap - ky * 3;
         const int Hup = p.Hin << p.up, Wup = p.Win << p.up;
         const int yi = (ayx[j] >> 16) + ky, xi = (int)(short)(ayx[j] & 0xffff) + kx;
-        const bool ok = (yi >= 0) & (yi < Hup) & (xi >= 0) & (xi < Wup);
+        const bool ok = conv_tap_inside(yi, xi, Hup, Wup);
         const int ys = yi >> p.up, xs = xi >> p.up;
         const unsigned short* src = ok ? p.A + ci0 + (aoff[j] + (unsigned)(ys * p.Win + xs) * (unsigned)p.lda) : idf_zero_page + dc * 8;
         dma16_v(src, dst);
@@ -801,7 +779,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
     }
   };
   auto advance_loader = [&]() {
-    if (CONV) { ci0 += BKT; if (ci0 >= p.Cin) { ci0 = 0; ++tap; } }
+    if (CONV) conv_tap_step(p, BKT, tap, ci0);
     if (++l_kt == l_nk) {
       l_kt = 0;
       l_seq += seq_step;

@@ -7,9 +7,10 @@
 // The MFMA "A" operand is the WEIGHT tile and "B" the activation tile, so every lane ends up owning 4 consecutive
 // output columns of one output row: epilogue = 8-byte packed stores, float4 bias loads, in-register GEGLU.
 //
-// Three K-loop variants share the tile epilogue: 1 = register-staged (conv gather), 2 = LDS-DMA double buffer, 3 = LDS-DMA ring with
-// its K-tiles in flight from the first instruction (the latency kernel of the small-batch launches, round 4); the persistent
-// 256 x {320,256,128} kernel that takes every launch big enough to fill the chip is gemm_big.hip.
+// Three K-loop variants share one core (gemm_core.h) and the tile epilogue: 1 = register-staged, the conv kernel; 2 = LDS-DMA double
+// buffer, the dense kernel; 3 = LDS-DMA ring with its K-tiles in flight from the first instruction (the latency kernel of the
+// small-batch launches, round 4; dense and conv); the persistent 256 x {320,256,128} kernel that takes every launch big enough to
+// fill the chip is gemm_big.hip.
 //
 // Roofline: MFMA-bound (2.5 PFLOP/s dense bf16); algorithmic flops = 2*M*N*K.
 #include "gemm_core.h"
@@ -26,7 +27,14 @@ namespace {
 #endif
 constexpr int LSTR = 72;   // LDS row stride in elements (144 B)
 
-// Tile epilogue shared by both K-loop variants (see the comment inside).
+// dynamic LDS of an LDS-DMA kernel (variants 2 / 3): `stages` K-tile images of linear 128-B rows, or the epilogue's fp32 staging
+// where that is larger
+template <int BM, int BN, int WM, int WN> constexpr int dma_lds_bytes(int stages) {
+  const int kloop = stages * (BM + BN) * 64 * 2, cstage = 4 * WM * (WN + 4) * 4;
+  return kloop > cstage ? kloop : cstage;
+}
+
+// Tile epilogue shared by the three K-loop variants (see the comment inside).
 template <int DT, int BM, int BN, int WM, int WN, int KLOOP_LDS_BYTES>
 __device__ __forceinline__ void tile_epilogue(const CoreParams& p, f32x16 (&acc)[WN / 32][WM / 32], unsigned short* smem,
                                               int m0, int n0, int bz, int wm, int wn, int lane, int wave) {
@@ -132,7 +140,9 @@ __device__ __forceinline__ void tile_epilogue(const CoreParams& p, f32x16 (&acc)
   }
 }
 
-template <int DT, int BM, int BN, int WM, int WN, bool CONV>
+// K-loop variant 1, the conv kernel: both operand tiles are staged through registers (the activation gather must zero its padding
+// taps), two K-tiles ahead of the MFMAs.
+template <int DT, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const CoreParams p) {
   constexpr int TM = WM / 32, TN = WN / 32;
   constexpr int WAVES_N = BN / WN;
@@ -145,81 +155,50 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const CoreParams p) {
   const int lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, hi = lane >> 5;
   const int wn = wave % WAVES_N, wm = wave / WAVES_N;
-  // XCD-aware tile order: workgroup L runs on XCD L % 8 (8 private L2s); give each XCD a CONTIGUOUS chunk of the
-  // n-fastest tile list so the n-tiles that share one activation m-tile hit the same L2 (bijective for any count).
-  int tile;
-  {
-    const int T = gridDim.x, L = blockIdx.x;
-    const int q = T >> 3, r = T & 7, xcd = L & 7, i = L >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  const int tiles_n = (p.N + BN - 1) / BN;
-  const int m_tile = tile / tiles_n;
-  const int n0 = (tile - m_tile * tiles_n) * BN, m0 = m_tile * BM;
-  const int bz = (p.splitk > 1) ? 0 : blockIdx.z;            // split-K launches are never batched
-
-  const unsigned short* Wb = p.W + (size_t)bz * p.strideW;
-  const unsigned short* Ab = p.A + (size_t)bz * p.strideA;
+  TileSlice t;
+  tile_slice<BM, BN>(p, xcd_tile(blockIdx.x, gridDim.x), t);
+  const int nk = t.nk;                                 // K-tiles of this block
 
   // ---- staging roles: thread -> (16-B chunk c along k, rows r0 + 32 i)
   const int c = tid & 7, r0 = tid >> 3;
   const unsigned short* wrow[WR];
 #pragma unroll
   for (int i = 0; i < WR; ++i) {
-    int n = min(n0 + r0 + 32 * i, p.N - 1);
-    wrow[i] = Wb + (size_t)n * p.ldw + c * 8;
+    int n = min(t.n0 + r0 + 32 * i, p.N - 1);
+    wrow[i] = t.Wb + (size_t)n * p.ldw + c * 8;
   }
-  const unsigned short* arow[AR];
-  int ay[AR], ax[AR];                                  // conv: output pixel coords (pre-multiplied by stride, -1)
+  const unsigned short* arow[AR];                      // image base + chunk
+  int ay[AR], ax[AR];                                  // window origin of the row's output pixel
 #pragma unroll
   for (int i = 0; i < AR; ++i) {
-    int m = min(m0 + r0 + 32 * i, p.M - 1);
-    if (CONV) {
-      int hw = p.Ho * p.Wo;
-      int b = m / hw, rem = m - b * hw;
-      int yo = rem / p.Wo, xo = rem - yo * p.Wo;
-      ay[i] = yo * p.stride - p.pad_lo;
-      ax[i] = xo * p.stride - p.pad_lo;
-      arow[i] = Ab + (size_t)b * p.Hin * p.Win * p.lda + c * 8;
-    } else {
-      ay[i] = ax[i] = 0;
-      arow[i] = Ab + (size_t)m * p.lda + c * 8;
-    }
+    int m = min(t.m0 + r0 + 32 * i, p.M - 1);
+    arow[i] = t.Ab + conv_row_origin(p, m, ay[i], ax[i]) + c * 8;
   }
-  const int nk_all = p.K / BK;
-  const int kt_begin = (p.splitk > 1) ? blockIdx.z * p.kt_per_slice : 0;
-  const int nk = (p.splitk > 1) ? min(p.kt_per_slice, nk_all - kt_begin) : nk_all;   // K-tiles of this block
-  int tap = 0, ci0 = 0;                                // conv: K-tile -> (3x3 tap, channel offset)
-  if (CONV) { tap = (kt_begin * BK) / p.Cin; ci0 = kt_begin * BK - tap * p.Cin; }
+  int tap, ci0;                                        // K-tile -> (3x3 tap, channel offset)
+  conv_tap_at(p, t.kt_begin * BK, tap, ci0);
 
   // two register sets: tile kt+1 waits in one while tile kt+2 is being fetched into the other (2-deep prefetch,
   // so a global load has two K-tile iterations of MFMA time to land before its ds_write needs it)
   u32x4 raA[AR], rwA[WR], raB[AR], rwB[WR];
-  unsigned okA = 0, okB = 0;                           // conv: per-row 'tap inside the image' bits of the staged tile
+  unsigned okA = 0, okB = 0;                           // per-row 'tap inside the image' bits of the staged tile
   auto load_tile = [&](int kt, u32x4* ra, u32x4* rw, unsigned& okbits) {
 #pragma unroll
-    for (int i = 0; i < WR; ++i) rw[i] = *reinterpret_cast<const u32x4*>(wrow[i] + (size_t)(kt_begin + kt) * BK);
-    if (CONV) {
-      const int ky = tap / 3, kx = tap - ky * 3;
-      const int Hup = p.Hin << p.up, Wup = p.Win << p.up;
-      unsigned bits = 0;
+    for (int i = 0; i < WR; ++i) rw[i] = *reinterpret_cast<const u32x4*>(wrow[i] + (size_t)(t.kt_begin + kt) * BK);
+    const int ky = tap / 3, kx = tap - ky * 3;
+    const int Hup = p.Hin << p.up, Wup = p.Win << p.up;
+    unsigned bits = 0;
 #pragma unroll
-      for (int i = 0; i < AR; ++i) {
-        const int yi = ay[i] + ky, xi = ax[i] + kx;
-        const bool ok = (yi >= 0) & (yi < Hup) & (xi >= 0) & (xi < Wup);
-        // UNCONDITIONAL load from a clamped (always valid) pixel; the padding taps are zeroed at ds_write time
-        // (store_tile) so the number of outstanding loads is static and the counted vmcnt waits stay exact.
-        const int ys = min(max(yi, 0), Hup - 1) >> p.up, xs = min(max(xi, 0), Wup - 1) >> p.up;
-        ra[i] = *reinterpret_cast<const u32x4*>(arow[i] + ((size_t)ys * p.Win + xs) * p.lda + ci0);
-        bits |= (ok ? 1u : 0u) << i;
-      }
-      okbits = bits;
-      ci0 += BK;
-      if (ci0 >= p.Cin) { ci0 = 0; ++tap; }
-    } else {
-#pragma unroll
-      for (int i = 0; i < AR; ++i) ra[i] = *reinterpret_cast<const u32x4*>(arow[i] + (size_t)(kt_begin + kt) * BK);
+    for (int i = 0; i < AR; ++i) {
+      const int yi = ay[i] + ky, xi = ax[i] + kx;
+      const bool ok = conv_tap_inside(yi, xi, Hup, Wup);
+      // UNCONDITIONAL load from a clamped (always valid) pixel; the padding taps are zeroed at ds_write time
+      // (store_tile) so the number of outstanding loads is static and the counted vmcnt waits stay exact.
+      const int ys = min(max(yi, 0), Hup - 1) >> p.up, xs = min(max(xi, 0), Wup - 1) >> p.up;
+      ra[i] = *reinterpret_cast<const u32x4*>(arow[i] + ((size_t)ys * p.Win + xs) * p.lda + ci0);
+      bits |= (ok ? 1u : 0u) << i;
     }
+    okbits = bits;
+    conv_tap_step(p, BK, tap, ci0);
   };
   auto store_tile = [&](int buf, const u32x4* ra, const u32x4* rw, unsigned okbits) {
     unsigned short* Al = smem + buf * BUF;
@@ -227,10 +206,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const CoreParams p) {
 #pragma unroll
     for (int i = 0; i < AR; ++i) {
       u32x4 v = ra[i];
-      if (CONV) {
-        const unsigned keep = ((okbits >> i) & 1u) ? 0xffffffffu : 0u;
-        v[0] &= keep; v[1] &= keep; v[2] &= keep; v[3] &= keep;
-      }
+      const unsigned keep = ((okbits >> i) & 1u) ? 0xffffffffu : 0u;
+      v[0] &= keep; v[1] &= keep; v[2] &= keep; v[3] &= keep;
       *reinterpret_cast<u32x4*>(Al + (r0 + 32 * i) * LSTR + c * 8) = v;
     }
 #pragma unroll
@@ -238,39 +215,10 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const CoreParams p) {
   };
 
   f32x16 acc[TN][TM];
-#pragma unroll
-  for (int a = 0; a < TN; ++a)
-#pragma unroll
-    for (int b = 0; b < TM; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-
+  clear_acc(acc);
   auto compute = [&](int buf) {
     const unsigned short* Al = smem + buf * BUF;
-    const unsigned short* Wl = Al + BM * LSTR;
-    const unsigned short* af_base = Al + (wm * WM + l31) * LSTR + hi * 8;
-    const unsigned short* wf_base = Wl + (wn * WN + l31) * LSTR + hi * 8;
-    // fragment reads of K-step ks+1 are issued BEFORE the MFMAs of K-step ks (register double-buffer), so the LDS
-    // latency (~100+ cycles) hides under 4-8 MFMAs instead of stalling every K-step (the compiler does not do this).
-    u32x4 wf[2][TN], af[2][TM];
-#pragma unroll
-    for (int a = 0; a < TN; ++a) wf[0][a] = *reinterpret_cast<const u32x4*>(wf_base + a * 32 * LSTR);
-#pragma unroll
-    for (int b = 0; b < TM; ++b) af[0][b] = *reinterpret_cast<const u32x4*>(af_base + b * 32 * LSTR);
-#pragma unroll
-    for (int ks = 0; ks < BK / 16; ++ks) {
-      const int cur = ks & 1, nxt = cur ^ 1;
-      if (ks + 1 < BK / 16) {
-#pragma unroll
-        for (int a = 0; a < TN; ++a) wf[nxt][a] = *reinterpret_cast<const u32x4*>(wf_base + a * 32 * LSTR + (ks + 1) * 16);
-#pragma unroll
-        for (int b = 0; b < TM; ++b) af[nxt][b] = *reinterpret_cast<const u32x4*>(af_base + b * 32 * LSTR + (ks + 1) * 16);
-      }
-#pragma unroll
-      for (int a = 0; a < TN; ++a)
-#pragma unroll
-        for (int b = 0; b < TM; ++b) acc[a][b] = Elem<DT>::mfma32(wf[cur][a], af[cur][b], acc[a][b]);
-    }
+    ktile_mfma<DT, TN, TM, LSTR, false>(acc, Al + BM * LSTR + (wn * WN + l31) * LSTR, Al + (wm * WM + l31) * LSTR, hi, 0);
   };
 
   load_tile(0, raA, rwA, okA);
@@ -312,29 +260,23 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const CoreParams p) {
     compute(0);
   }
 
-  tile_epilogue<DT, BM, BN, WM, WN, 2 * (BM + BN) * LSTR * 2>(p, acc, smem, m0, n0, bz, wm, wn, lane, wave);
+  tile_epilogue<DT, BM, BN, WM, WN, 2 * (BM + BN) * LSTR * 2>(p, acc, smem, t.m0, t.n0, t.bz, wm, wn, lane, wave);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// K-loop variant 2: LDS-DMA staging (global_load_lds_dwordx4) for every DENSE operand tile (the weight tile always, the
-// activation tile unless CONV).  The VGPR -> LDS store path (ds_write_b128 ~79 B/clk/CU) was the busiest pipe of
-// variant 1 -- 64 KB of tile stores per CU per K-tile pair against 1024 MFMA cycles; the DMA path bypasses it and frees
-// the staging registers.  An LDS-DMA instruction writes wave-uniform base + lane*16 B, so the tile image is LINEAR
-// 128-B rows (64 elements); bank conflicts of the ds_read_b128 fragment reads are removed by an XOR swizzle applied on
-// the per-lane GLOBAL source address and, identically, on the reads:  LDS slot = k-chunk ^ ((row >> 1) & 7).
-// The conv activation gather keeps the register path (padding taps must be zeroed) and stores into the same image.
+// K-loop variant 2, the dense kernel: LDS-DMA staging (global_load_lds_dwordx4) of both operand tiles.  The VGPR -> LDS store
+// path (ds_write_b128 ~79 B/clk/CU) was the busiest pipe of variant 1 -- 64 KB of tile stores per CU per K-tile pair against
+// 1024 MFMA cycles; the DMA path bypasses it and frees the staging registers.  An LDS-DMA instruction writes wave-uniform
+// base + lane*16 B, so the tile image is LINEAR 128-B rows (64 elements); bank conflicts of the ds_read_b128 fragment reads are
+// removed by an XOR swizzle applied on the per-lane GLOBAL source address and, identically, on the reads (gemm_core.h).
 // ------------------------------------------------------------------------------------------------------------------
-template <int DT, int BM, int BN, int WM, int WN, bool CONV>
+template <int DT, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256, 2) void gemm_kernel_dma(const CoreParams p) {
   constexpr int TM = WM / 32, TN = WN / 32;
   constexpr int WAVES_N = BN / WN;
   constexpr int RS = 64;                                // LDS row stride (elements) = BK, no padding
   constexpr int BUF = (BM + BN) * RS;
   constexpr int W_INST = BN / 8 / 4, A_INST = BM / 8 / 4;     // DMA instructions (8 rows each) per wave per tile
-  constexpr int AR = BM / 32;
-  constexpr int KLOOP_LDS = 2 * BUF * 2;
-  constexpr int CSTAGE = 4 * WM * (WN + 4) * 4;
-  constexpr int LDS_BYTES = KLOOP_LDS > CSTAGE ? KLOOP_LDS : CSTAGE;
   static_assert((BM / WM) * (BN / WN) == 4, "4 waves per workgroup");
   extern __shared__ __attribute__((aligned(16))) unsigned short smem[];
 
@@ -342,63 +284,16 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel_dma(const CoreParams p) {
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
   const int wn = wave % WAVES_N, wm = wave / WAVES_N;
-  int tile;
-  {
-    const int T = gridDim.x, L = blockIdx.x;
-    const int q = T >> 3, r = T & 7, xcd = L & 7, i = L >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  const int tiles_n = (p.N + BN - 1) / BN;
-  const int m_tile = tile / tiles_n;
-  const int n0 = (tile - m_tile * tiles_n) * BN, m0 = m_tile * BM;
-  const int bz = (p.splitk > 1) ? 0 : blockIdx.z;
-  const unsigned short* Wb = p.W + (size_t)bz * p.strideW;
-  const unsigned short* Ab = p.A + (size_t)bz * p.strideA;
+  TileSlice t;
+  tile_slice<BM, BN>(p, xcd_tile(blockIdx.x, gridDim.x), t);
+  const int nk = t.nk;
 
-  const int nk_all = p.K / BK;
-  const int kt_begin = (p.splitk > 1) ? blockIdx.z * p.kt_per_slice : 0;
-  const int nk = (p.splitk > 1) ? min(p.kt_per_slice, nk_all - kt_begin) : nk_all;
-
-  // ---- DMA roles: instruction j of this wave covers tile rows 8*(wave + 4 j) .. +7; lane -> (row r = lane>>3, slot c)
-  const int dr = lane >> 3, dc = lane & 7;
   const unsigned short* wsrc[W_INST];
-#pragma unroll
-  for (int j = 0; j < W_INST; ++j) {
-    const int row = 8 * (wave + 4 * j) + dr;                     // tile-local row
-    const int n = min(n0 + row, p.N - 1);
-    wsrc[j] = Wb + (size_t)n * p.ldw + (size_t)kt_begin * BK + ((dc ^ ((row >> 1) & 7)) * 8);
-  }
   const unsigned short* asrc[A_INST];
-  if (!CONV) {
 #pragma unroll
-    for (int j = 0; j < A_INST; ++j) {
-      const int row = 8 * (wave + 4 * j) + dr;
-      const int m = min(m0 + row, p.M - 1);
-      asrc[j] = Ab + (size_t)m * p.lda + (size_t)kt_begin * BK + ((dc ^ ((row >> 1) & 7)) * 8);
-    }
-  }
-  // ---- conv activation gather (register path): thread -> (16-B chunk c, rows r0 + 32 i)
-  const int c = tid & 7, r0 = tid >> 3;
-  const unsigned short* arow[AR];
-  int ay[AR], ax[AR];
-  int tap = 0, ci0 = 0;
-  if (CONV) {
+  for (int j = 0; j < W_INST; ++j) wsrc[j] = dma_src_row(t.Wb, p.ldw, t.n0, p.N, (size_t)t.kt_begin * BK, wave, j, lane);
 #pragma unroll
-    for (int i = 0; i < AR; ++i) {
-      const int m = min(m0 + r0 + 32 * i, p.M - 1);
-      const int hw = p.Ho * p.Wo;
-      const int b = m / hw, rem = m - b * hw;
-      const int yo = rem / p.Wo, xo = rem - yo * p.Wo;
-      ay[i] = yo * p.stride - p.pad_lo;
-      ax[i] = xo * p.stride - p.pad_lo;
-      arow[i] = Ab + (size_t)b * p.Hin * p.Win * p.lda + c * 8;
-    }
-    tap = (kt_begin * BK) / p.Cin;
-    ci0 = kt_begin * BK - tap * p.Cin;
-  }
-  const int a_sw = (c ^ ((r0 >> 1) & 7)) * 8;            // (row>>1)&7 == (r0>>1)&7 for rows r0 + 32 i
-  u32x4 ra[AR];
-  unsigned okbits = 0;
+  for (int j = 0; j < A_INST; ++j) asrc[j] = dma_src_row(t.Ab, p.lda, t.m0, p.M, (size_t)t.kt_begin * BK, wave, j, lane);
 
   auto dma_tile = [&](int kt, int buf) {                // enqueue the LDS-DMA of K-tile kt into LDS buffer buf
     unsigned short* Al = smem + buf * BUF;
@@ -407,93 +302,28 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel_dma(const CoreParams p) {
     for (int j = 0; j < W_INST; ++j)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wsrc[j] + (size_t)kt * BK),
                                        (__attribute__((address_space(3))) void*)(Wl + 8 * (wave + 4 * j) * RS), 16, 0, 0);
-    if (!CONV) {
 #pragma unroll
-      for (int j = 0; j < A_INST; ++j)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(asrc[j] + (size_t)kt * BK),
-                                         (__attribute__((address_space(3))) void*)(Al + 8 * (wave + 4 * j) * RS), 16, 0, 0);
-    }
-  };
-  auto gather_tile = [&]() {                            // conv: issue the activation gather of the next K-tile
-    const int ky = tap / 3, kx = tap - ky * 3;
-    const int Hup = p.Hin << p.up, Wup = p.Win << p.up;
-    unsigned bits = 0;
-#pragma unroll
-    for (int i = 0; i < AR; ++i) {
-      const int yi = ay[i] + ky, xi = ax[i] + kx;
-      const bool ok = (yi >= 0) & (yi < Hup) & (xi >= 0) & (xi < Wup);
-      const int ys = min(max(yi, 0), Hup - 1) >> p.up, xs = min(max(xi, 0), Wup - 1) >> p.up;
-      ra[i] = *reinterpret_cast<const u32x4*>(arow[i] + ((size_t)ys * p.Win + xs) * p.lda + ci0);
-      bits |= (ok ? 1u : 0u) << i;
-    }
-    okbits = bits;
-    ci0 += BK;
-    if (ci0 >= p.Cin) { ci0 = 0; ++tap; }
-  };
-  auto scatter_tile = [&](int buf) {                    // conv: zero the padding taps and store into the swizzled image
-    unsigned short* Al = smem + buf * BUF;
-#pragma unroll
-    for (int i = 0; i < AR; ++i) {
-      u32x4 v = ra[i];
-      const unsigned keep = ((okbits >> i) & 1u) ? 0xffffffffu : 0u;
-      v[0] &= keep; v[1] &= keep; v[2] &= keep; v[3] &= keep;
-      *reinterpret_cast<u32x4*>(Al + (r0 + 32 * i) * RS + a_sw) = v;
-    }
+    for (int j = 0; j < A_INST; ++j)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(asrc[j] + (size_t)kt * BK),
+                                       (__attribute__((address_space(3))) void*)(Al + 8 * (wave + 4 * j) * RS), 16, 0, 0);
   };
 
   f32x16 acc[TN][TM];
-#pragma unroll
-  for (int a = 0; a < TN; ++a)
-#pragma unroll
-    for (int b = 0; b < TM; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-
-  const int f_sw = (l31 >> 1) & 7;                      // read-side swizzle: fragment rows are (multiple of 32) + l31
+  clear_acc(acc);
+  const int f_sw = (l31 >> 1) & 7;                      // read-side swizzle
   auto compute = [&](int buf) {
     const unsigned short* Al = smem + buf * BUF;
-    const unsigned short* Wl = Al + BM * RS;
-    const unsigned short* af_base = Al + (wm * WM + l31) * RS;
-    const unsigned short* wf_base = Wl + (wn * WN + l31) * RS;
-    u32x4 wf[2][TN], af[2][TM];                         // register double-buffered fragments (see variant 1)
-    {
-      const int slot = (hi ^ f_sw) * 8;
-#pragma unroll
-      for (int a = 0; a < TN; ++a) wf[0][a] = *reinterpret_cast<const u32x4*>(wf_base + a * 32 * RS + slot);
-#pragma unroll
-      for (int b = 0; b < TM; ++b) af[0][b] = *reinterpret_cast<const u32x4*>(af_base + b * 32 * RS + slot);
-    }
-#pragma unroll
-    for (int ks = 0; ks < BK / 16; ++ks) {
-      const int cur = ks & 1, nxt = cur ^ 1;
-      if (ks + 1 < BK / 16) {
-        const int slot = (((ks + 1) * 2 + hi) ^ f_sw) * 8;
-#pragma unroll
-        for (int a = 0; a < TN; ++a) wf[nxt][a] = *reinterpret_cast<const u32x4*>(wf_base + a * 32 * RS + slot);
-#pragma unroll
-        for (int b = 0; b < TM; ++b) af[nxt][b] = *reinterpret_cast<const u32x4*>(af_base + b * 32 * RS + slot);
-      }
-#pragma unroll
-      for (int a = 0; a < TN; ++a)
-#pragma unroll
-        for (int b = 0; b < TM; ++b) acc[a][b] = Elem<DT>::mfma32(wf[cur][a], af[cur][b], acc[a][b]);
-    }
+    ktile_mfma<DT, TN, TM, RS, true>(acc, Al + BM * RS + (wn * WN + l31) * RS, Al + (wm * WM + l31) * RS, hi, f_sw);
   };
 
   dma_tile(0, 0);
-  if (CONV) { gather_tile(); scatter_tile(0); }
   __syncthreads();                                      // drains vmcnt: tile 0 landed
   for (int kt = 0; kt < nk; ++kt) {
-    const bool more = (kt + 1 < nk);
-    if (more) {
-      dma_tile(kt + 1, (kt + 1) & 1);                   // lands during the MFMAs of tile kt
-      if (CONV) gather_tile();
-    }
+    if (kt + 1 < nk) dma_tile(kt + 1, (kt + 1) & 1);    // lands during the MFMAs of tile kt
     compute(kt & 1);
-    if (CONV && more) scatter_tile((kt + 1) & 1);
     __syncthreads();                                    // (kt+1) complete and visible; buffer kt&1 free for tile kt+2
   }
-  tile_epilogue<DT, BM, BN, WM, WN, LDS_BYTES>(p, acc, smem, m0, n0, bz, wm, wn, lane, wave);
+  tile_epilogue<DT, BM, BN, WM, WN, dma_lds_bytes<BM, BN, WM, WN>(2)>(p, acc, smem, t.m0, t.n0, t.bz, wm, wn, lane, wave);
 }
 
 // ---- K-loop variant 3 (round 4): the LATENCY kernel.  The launches the persistent kernel declines (a 2-row forward is ~250
@@ -502,15 +332,11 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel_dma(const CoreParams p) {
 // whatever the shape (profiles/r03_shape_profile_B2.log).  Same tile, LDS image, swizzle, fragment reads and epilogue as
 // variant 2, but an NS-stage ring with NS - 1 K-tiles in flight from the first instruction (all of K = 320), counted
 // s_waitcnt vmcnt instead of a drain per tile, and the conv activation tile arrives by LDS-DMA too (a lane whose tap is
-// padding reads a zero page, like the persistent kernel's loader).  LDS-DMA is inline assembly: with the builtin the
+// padding reads a zero page, like the persistent kernel's loader).  LDS-DMA is inline assembly (common.h): with the builtin the
 // compiler orders every later ds_read behind ALL outstanding DMA.  One workgroup per CU (96-144 KB of LDS): meant for launches
 // of at most a few hundred tiles -- the dispatcher's rule is in launch().
-__device__ __attribute__((aligned(128))) unsigned short ring_zero_page[64];   // zero-initialised device memory
+IDF_ZERO_PAGE(ring_zero_page);
 
-__device__ __forceinline__ void ring_dma16(const void* addr /* per lane */, const void* lds_lane0) {
-  const unsigned l = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lds_lane0);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(l), "v"(addr) : "memory");
-}
 // at most `ahead` K-tiles (PT LDS-DMA instructions of this wave each) may still be in flight behind the tile waited for
 template <int PT, int MAXA> __device__ __forceinline__ void ring_wait(int ahead) {
   if constexpr (MAXA <= 0) {
@@ -530,9 +356,7 @@ __global__ __launch_bounds__(256, 1) void gemm_kernel_ring(const CoreParams p) {
   constexpr int BUF = (BM + BN) * RS;                   // elements per ring stage
   constexpr int W_INST = BN / 8 / 4, A_INST = BM / 8 / 4;     // DMA instructions (8 rows each) per wave per tile
   constexpr int PER_TILE = W_INST + A_INST;
-  constexpr int KLOOP_LDS = NS * BUF * 2;
-  constexpr int CSTAGE = 4 * WM * (WN + 4) * 4;
-  constexpr int LDS_BYTES = KLOOP_LDS > CSTAGE ? KLOOP_LDS : CSTAGE;
+  constexpr int LDS_BYTES = dma_lds_bytes<BM, BN, WM, WN>(NS);
   static_assert((BM / WM) * (BN / WN) == 4, "4 waves per workgroup");
   static_assert(NS >= 3 && LDS_BYTES <= 160 * 1024, "ring must fit the CU's LDS");
   extern __shared__ __attribute__((aligned(16))) unsigned short smem[];
@@ -541,119 +365,60 @@ __global__ __launch_bounds__(256, 1) void gemm_kernel_ring(const CoreParams p) {
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
   const int wn = wave % WAVES_N, wm = wave / WAVES_N;
-  int tile;
-  {
-    const int T = gridDim.x, L = blockIdx.x;
-    const int q = T >> 3, r = T & 7, xcd = L & 7, i = L >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
-  const int tiles_n = (p.N + BN - 1) / BN;
-  const int m_tile = tile / tiles_n;
-  const int n0 = (tile - m_tile * tiles_n) * BN, m0 = m_tile * BM;
-  const int bz = (p.splitk > 1) ? 0 : blockIdx.z;
-  const unsigned short* Wb = p.W + (size_t)bz * p.strideW;
-  const unsigned short* Ab = p.A + (size_t)bz * p.strideA;
+  TileSlice t;
+  tile_slice<BM, BN>(p, xcd_tile(blockIdx.x, gridDim.x), t);
+  const int nk = t.nk;
 
-  const int nk_all = p.K / BK;
-  const int kt_begin = (p.splitk > 1) ? blockIdx.z * p.kt_per_slice : 0;
-  const int nk = (p.splitk > 1) ? min(p.kt_per_slice, nk_all - kt_begin) : nk_all;
-
-  // ---- DMA roles: instruction j of this wave covers tile rows 8*(wave + 4 j) .. +7; lane -> (row r = lane>>3, slot c);
-  // the 16-B slot of a row is XOR-swizzled on the SOURCE side (slot c of LDS row `row` holds global chunk c ^ ((row>>1)&7))
-  const int dr = lane >> 3, dc = lane & 7;
+  const int dc = lane & 7;
   const unsigned short* wsrc[W_INST];
-#pragma unroll
-  for (int j = 0; j < W_INST; ++j) {
-    const int row = 8 * (wave + 4 * j) + dr;                     // tile-local row
-    const int n = min(n0 + row, p.N - 1);
-    wsrc[j] = Wb + (size_t)n * p.ldw + (size_t)kt_begin * BK + ((dc ^ ((row >> 1) & 7)) * 8);
-  }
+  dma_src_rows(wsrc, t.Wb, p.ldw, t.n0, p.N, (size_t)t.kt_begin * BK, wave, lane);
   const unsigned short* asrc[A_INST];                            // dense: row pointer at kt_begin; conv: image base + chunk
-  int ay[A_INST], ax[A_INST];
-#pragma unroll
-  for (int j = 0; j < A_INST; ++j) {
-    const int row = 8 * (wave + 4 * j) + dr;
-    const int m = min(m0 + row, p.M - 1);
-    const int ch = (dc ^ ((row >> 1) & 7)) * 8;
-    if (!CONV) {
-      asrc[j] = Ab + (size_t)m * p.lda + (size_t)kt_begin * BK + ch;
-      ay[j] = ax[j] = 0;
-    } else {
-      const int hw = p.Ho * p.Wo;
-      const int b = m / hw, rem = m - b * hw;
-      const int yo = rem / p.Wo, xo = rem - yo * p.Wo;
-      ay[j] = yo * p.stride - p.pad_lo;
-      ax[j] = xo * p.stride - p.pad_lo;
-      asrc[j] = Ab + (size_t)b * p.Hin * p.Win * p.lda + ch;
-    }
-  }
+  [[maybe_unused]] int ay[A_INST], ax[A_INST];
   int tap = 0, ci0 = 0;                                          // conv: tap / first input channel of the next K-tile to issue
-  if (CONV) { tap = (kt_begin * BK) / p.Cin; ci0 = kt_begin * BK - tap * p.Cin; }
+  if constexpr (!CONV) {
+    dma_src_rows(asrc, t.Ab, p.lda, t.m0, p.M, (size_t)t.kt_begin * BK, wave, lane);
+  } else {
+#pragma unroll
+    for (int j = 0; j < A_INST; ++j) {
+      const int row = dma_row(wave, j, lane);
+      const int m = min(t.m0 + row, p.M - 1);
+      asrc[j] = t.Ab + conv_row_origin(p, m, ay[j], ax[j]) + dma_chunk(row, lane);
+    }
+    conv_tap_at(p, t.kt_begin * BK, tap, ci0);
+  }
   int kt_issue = 0, st_issue = 0;                                // next K-tile to enqueue and the ring stage it goes to
 
   auto issue_tile = [&]() {
     unsigned short* Al = smem + st_issue * BUF;
     unsigned short* Wl = Al + BM * RS;
 #pragma unroll
-    for (int j = 0; j < W_INST; ++j) ring_dma16(wsrc[j] + (size_t)kt_issue * BK, Wl + 8 * (wave + 4 * j) * RS);
-    if (!CONV) {
+    for (int j = 0; j < W_INST; ++j) dma16_v(wsrc[j] + (size_t)kt_issue * BK, lds_addr(Wl + 8 * (wave + 4 * j) * RS));
+    if constexpr (!CONV) {
 #pragma unroll
-      for (int j = 0; j < A_INST; ++j) ring_dma16(asrc[j] + (size_t)kt_issue * BK, Al + 8 * (wave + 4 * j) * RS);
+      for (int j = 0; j < A_INST; ++j) dma16_v(asrc[j] + (size_t)kt_issue * BK, lds_addr(Al + 8 * (wave + 4 * j) * RS));
     } else {
       const int ky = tap / 3, kx = tap - ky * 3;
       const int Hup = p.Hin << p.up, Wup = p.Win << p.up;
 #pragma unroll
       for (int j = 0; j < A_INST; ++j) {
         const int yi = ay[j] + ky, xi = ax[j] + kx;
-        const bool ok = (yi >= 0) & (yi < Hup) & (xi >= 0) & (xi < Wup);
+        const bool ok = conv_tap_inside(yi, xi, Hup, Wup);
         const int ys = yi >> p.up, xs = xi >> p.up;
         const unsigned short* src = ok ? asrc[j] + ((size_t)ys * p.Win + xs) * p.lda + ci0 : ring_zero_page + dc * 8;
-        ring_dma16(src, Al + 8 * (wave + 4 * j) * RS);
+        dma16_v(src, lds_addr(Al + 8 * (wave + 4 * j) * RS));
       }
-      ci0 += BK;
-      if (ci0 >= p.Cin) { ci0 = 0; ++tap; }
+      conv_tap_step(p, BK, tap, ci0);
     }
     ++kt_issue;
     st_issue = (st_issue + 1 == NS) ? 0 : st_issue + 1;
   };
 
   f32x16 acc[TN][TM];
-#pragma unroll
-  for (int a = 0; a < TN; ++a)
-#pragma unroll
-    for (int b = 0; b < TM; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-
-  const int f_sw = (l31 >> 1) & 7;                      // read-side swizzle: fragment rows are (multiple of 32) + l31
+  clear_acc(acc);
+  const int f_sw = (l31 >> 1) & 7;                      // read-side swizzle
   auto compute = [&](int st) {
     const unsigned short* Al = smem + st * BUF;
-    const unsigned short* Wl = Al + BM * RS;
-    const unsigned short* af_base = Al + (wm * WM + l31) * RS;
-    const unsigned short* wf_base = Wl + (wn * WN + l31) * RS;
-    u32x4 wf[2][TN], af[2][TM];                         // register double-buffered fragments
-    {
-      const int slot = (hi ^ f_sw) * 8;
-#pragma unroll
-      for (int a = 0; a < TN; ++a) wf[0][a] = *reinterpret_cast<const u32x4*>(wf_base + a * 32 * RS + slot);
-#pragma unroll
-      for (int b = 0; b < TM; ++b) af[0][b] = *reinterpret_cast<const u32x4*>(af_base + b * 32 * RS + slot);
-    }
-#pragma unroll
-    for (int ks = 0; ks < BK / 16; ++ks) {
-      const int cur = ks & 1, nxt = cur ^ 1;
-      if (ks + 1 < BK / 16) {
-        const int slot = (((ks + 1) * 2 + hi) ^ f_sw) * 8;
-#pragma unroll
-        for (int a = 0; a < TN; ++a) wf[nxt][a] = *reinterpret_cast<const u32x4*>(wf_base + a * 32 * RS + slot);
-#pragma unroll
-        for (int b = 0; b < TM; ++b) af[nxt][b] = *reinterpret_cast<const u32x4*>(af_base + b * 32 * RS + slot);
-      }
-#pragma unroll
-      for (int a = 0; a < TN; ++a)
-#pragma unroll
-        for (int b = 0; b < TM; ++b) acc[a][b] = Elem<DT>::mfma32(wf[cur][a], af[cur][b], acc[a][b]);
-    }
+    ktile_mfma<DT, TN, TM, RS, true>(acc, Al + BM * RS + (wn * WN + l31) * RS, Al + (wm * WM + l31) * RS, hi, f_sw);
   };
 
   const int pre = min(NS - 1, nk);
@@ -667,7 +432,7 @@ __global__ __launch_bounds__(256, 1) void gemm_kernel_ring(const CoreParams p) {
     compute(st);
     st = (st + 1 == NS) ? 0 : st + 1;
   }
-  tile_epilogue<DT, BM, BN, WM, WN, LDS_BYTES>(p, acc, smem, m0, n0, bz, wm, wn, lane, wave);
+  tile_epilogue<DT, BM, BN, WM, WN, LDS_BYTES>(p, acc, smem, t.m0, t.n0, t.bz, wm, wn, lane, wave);
 }
 
 // out = epi(sum over K-slices) for split-K launches: one thread per 8 consecutive columns of one row
@@ -715,18 +480,17 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const CoreParams p) 
 
 // K-loop variant choice (measured on MI355X, profiles/r01_diag_B18_*): LDS-DMA staging wins for dense GEMMs
 // (+5..18 % on K >= 1280, ~0 on K = 320); the conv gather is faster with the 2-deep register prefetch of variant 1
-// (its activation tile cannot use DMA).  IDF_GEMM_DMA=0/1 forces one variant for A/B runs.
-// IDF_GEMM_VARIANT=1|2 forces one K-loop variant for A/B runs.  Default: LDS-DMA (2) for dense GEMMs, register
-// prefetch (1) for the conv gather.  A third variant (4-stage ring of 32-deep K-steps, 3 DMA steps in flight, counted
+// (its activation tile needs its padding taps zeroed on the way).  So variant 1 exists as the conv kernel and variant 2 as the
+// dense kernel only (launch_cfg).  A third variant (4-stage ring of 32-deep K-steps, 3 DMA steps in flight, counted
 // vmcnt + raw s_barrier) was built and measured SLOWER than variant 2 on every shape but one (744 vs 846 TF at 8192^3,
 // 485 vs 644 at K=1280: a barrier per 8 MFMAs costs more than the deeper prefetch buys) and was removed; numbers in
 // profiles/r01_diag_B18_gemm_ring_vs_dma.log.  That was THROUGHPUT on grids of thousands of tiles, two workgroups per CU; the
 // latency kernel above (round 4: 64-deep K-steps, one barrier per 16 MFMAs, one workgroup per CU) serves the opposite regime --
 // grids of <= 256 tiles, where a launch is a chain of dependent trips to memory -- and is chosen by tile count in launch().
 std::atomic<long long> idf_stat_gn_epi_launches{0};   // idf_conv3x3 calls whose GroupNorm partials came out of the epilogue (idf_get_stat)
-std::atomic<long long> idf_stat_ring_launches{0};
+std::atomic<long long> idf_stat_ring_launches{0};     // launches of the latency kernel (idf_get_stat)
 std::atomic<long long> idf_stat_gegluw_launches{0};   // GEGLU projections served by geglu640w_kernel (idf_get_stat)
-std::atomic<long long> idf_stat_qkvw_launches{0};     // fused q | k | v projections served by qkv320w_kernel (idf_get_stat)     // launches of the latency kernel (idf_get_stat)
+std::atomic<long long> idf_stat_qkvw_launches{0};     // fused q | k | v projections served by qkv320w_kernel (idf_get_stat)
 std::atomic<long long> idf_stat_projw_launches{0};    // N = K = 320 projections served by proj320s_kernel (idf_get_stat)
 int g_big_mode = -2;
 inline int gemm_big_mode() {
@@ -738,46 +502,49 @@ inline int gemm_big_mode() {
   return g_big_mode;
 }
 
-inline int kloop_variant(bool conv) {
-  static int v = -2;
-  if (v == -2) { const char* e = getenv("IDF_GEMM_VARIANT"); v = e ? atoi(e) : -1; }
-  if (v == 1 || v == 2) return v;
-  return conv ? 1 : 2;
+// the reducer of a split-K launch whose fp32 partial slabs cover rows [q.tail_m0, q.tail_m0 + q.tail_rows)
+template <int DT>
+void launch_reduce(const CoreParams& q, hipStream_t s) {
+  const size_t n8 = (size_t)q.tail_rows * ((q.N + 7) / 8);
+  hipLaunchKernelGGL(splitk_reduce_kernel<DT>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, q);
 }
 
-template <int DT, int BM, int BN, int WM, int WN, bool CONV>
-int launch_cfg(const CoreParams& p, int batch, hipStream_t s) {
-  const int variant = kloop_variant(CONV);
-  void (*kern)(const CoreParams) = gemm_kernel<DT, BM, BN, WM, WN, CONV>;
-  constexpr int cstage = 4 * WM * (WN + 4) * 4;
-  constexpr int kloop2 = 2 * (BM + BN) * 64 * 2;
-  int smem = 2 * (BM + BN) * LSTR * 2;
-  if (variant == 2) { kern = gemm_kernel_dma<DT, BM, BN, WM, WN, CONV>; smem = kloop2 > cstage ? kloop2 : cstage; }
-  static std::atomic<unsigned long long> attr_done[3];
-  if (const int e = idf_lds_optin(reinterpret_cast<const void*>(kern), smem, attr_done[variant])) return e;
+// One launch of the K-loop kernel KERN on BM x BN tiles: the LDS opt-in, `want` K-slices (the caller's rule; 1 = unsplit) fitted
+// to the workspace, the launch and, where K was split, the reducer.
+template <int DT, int BM, int BN, void (*KERN)(const CoreParams), int SMEM>
+int launch_kloop(const CoreParams& p, int batch, int want, hipStream_t s, std::atomic<long long>* launches = nullptr) {
+  static std::atomic<unsigned long long> attr_done{0};
+  if (const int e = idf_lds_optin(reinterpret_cast<const void*>(KERN), SMEM, attr_done)) return e;
   CoreParams q = p;
   const int tiles = ((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM);
   const int nk = p.K / BK;
   q.splitk = 1; q.kt_per_slice = nk;
   q.tail_m0 = 0; q.tail_rows = p.M;                         // uniform split-K: the partial slabs cover every row
-  // split-K when the tile grid cannot fill the 256 CUs (small-spatial / small-batch layers with long K)
-  if (batch == 1 && p.ws && !(p.epi & IDF_EPI_GEGLU) && tiles < 192 && nk >= 8) {
-    int want = (512 + tiles - 1) / tiles;
-    if (want > nk / 4) want = nk / 4;
-    if (want > 64) want = 64;
-    while (want > 1 && (size_t)want * p.M * p.N * sizeof(float) > p.ws_bytes) --want;
-    if (want > 1) {
-      q.kt_per_slice = (nk + want - 1) / want;
-      q.splitk = (nk + q.kt_per_slice - 1) / q.kt_per_slice;
-    }
+  while (want > 1 && (size_t)want * p.M * p.N * sizeof(float) > p.ws_bytes) --want;
+  if (want > 1) {
+    q.kt_per_slice = (nk + want - 1) / want;
+    q.splitk = (nk + q.kt_per_slice - 1) / q.kt_per_slice;
   }
   dim3 grid(tiles, 1, q.splitk > 1 ? q.splitk : batch);
-  hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, q);
-  if (q.splitk > 1) {
-    const size_t n8 = (size_t)q.M * ((q.N + 7) / 8);
-    hipLaunchKernelGGL(splitk_reduce_kernel<DT>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, q);
-  }
+  hipLaunchKernelGGL(KERN, grid, dim3(256), SMEM, s, q);
+  if (launches) ++*launches;
+  if (q.splitk > 1) launch_reduce<DT>(q, s);
   return idf_launch_status();
+}
+
+template <int DT, int BM, int BN, int WM, int WN, bool CONV>
+int launch_cfg(const CoreParams& p, int batch, hipStream_t s) {
+  const int tiles = ((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM);
+  const int nk = p.K / BK;
+  // split-K when the tile grid cannot fill the 256 CUs (small-spatial / small-batch layers with long K)
+  int want = 1;
+  if (batch == 1 && p.ws && !(p.epi & IDF_EPI_GEGLU) && tiles < 192 && nk >= 8) {
+    want = (512 + tiles - 1) / tiles;
+    if (want > nk / 4) want = nk / 4;
+    if (want > 64) want = 64;
+  }
+  if constexpr (CONV) return launch_kloop<DT, BM, BN, gemm_kernel<DT, BM, BN, WM, WN>, 2 * (BM + BN) * LSTR * 2>(p, batch, want, s);
+  else return launch_kloop<DT, BM, BN, gemm_kernel_dma<DT, BM, BN, WM, WN>, dma_lds_bytes<BM, BN, WM, WN>(2)>(p, batch, want, s);
 }
 
 // Latency kernel (variant 3) dispatch: taken when the tile grid has at most g_ring_tiles tiles (0 = never).
@@ -795,54 +562,33 @@ inline int gemm_ring_tiles() {
   return g_ring_tiles;
 }
 
+// least K-tiles per split-K slice of the latency kernel (4 / 8 / 16 / 32 give 5.49 / 5.29 / 5.73 / 6.07 ms of GEMM + conv per
+// 2-row forward, profiles/r04_ring_slice_length.log: shorter slices pay more reducer traffic than their parallelism buys)
+constexpr int RING_SLICE_KT = 8;
+
 // returns IDF_BIG_UNSUPPORTED when the launch is left to variants 1 / 2
 template <int DT, int BM, int BN, int WM, int WN, bool CONV, int NS>
 int launch_ring_cfg(const CoreParams& p, int batch, hipStream_t s) {
   const int tiles = ((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM);
   const int nk = p.K / BK;
   // the threshold counts WORKGROUPS: a batched launch multiplies the tile grid by its batch (the transposed-V GEMM of a 128-row
-  // forward: 20 tiles x 128 = 2560 workgroups of a kernel that runs one per CU on a 120-128 KB ring -- ADVICE r4); IDF_RING_BATCHED=1
-  // restores the round-4 rule (per-batch tile count) for A/B runs
-  static int batched_old = -1;
-  if (batched_old < 0) { const char* e = getenv("IDF_RING_BATCHED"); batched_old = (e && e[0] == '1') ? 1 : 0; }
-  if ((long long)tiles * (batched_old ? 1 : batch) > gemm_ring_tiles()) return IDF_BIG_UNSUPPORTED;
+  // forward: 20 tiles x 128 = 2560 workgroups of a kernel that runs one per CU on a 120-128 KB ring -- ADVICE r4;
+  // profiles/r05_ring_batched_ab.log)
+  if ((long long)tiles * batch > gemm_ring_tiles()) return IDF_BIG_UNSUPPORTED;
   const int slots = idf_num_cu();
   // a grid of 129 ... 191 tiles with a long K: variants 1 / 2 cut it into K-slices for their two workgroups per CU, this
   // kernel (one per CU) cannot -- throughput, not latency, decides there (3x3 conv 16^2 -> 32^2 at 2 rows: 105 vs 141 us)
   if (batch == 1 && p.ws && !(p.epi & IDF_EPI_GEGLU) && tiles * 2 > slots && tiles < 192 && nk >= 8) return IDF_BIG_UNSUPPORTED;
-  void (*kern)(const CoreParams) = gemm_kernel_ring<DT, BM, BN, WM, WN, CONV, NS>;
-  constexpr int cstage = 4 * WM * (WN + 4) * 4;
-  constexpr int kloop = NS * (BM + BN) * 64 * 2;
-  constexpr int smem = kloop > cstage ? kloop : cstage;
-  static std::atomic<unsigned long long> attr_done{0};
-  if (const int e = idf_lds_optin(reinterpret_cast<const void*>(kern), smem, attr_done)) return e;
-  CoreParams q = p;
-  q.splitk = 1; q.kt_per_slice = nk;
-  q.tail_m0 = 0; q.tail_rows = p.M;
-  // split-K towards one workgroup per CU (this kernel's occupancy), slices of >= 8 K-tiles (two to three trips to memory with
-  // the ring's depth) plus the reducer
-  // least K-tiles per slice: 8 (IDF_RING_SLICE_KT for A/B runs; 4 / 8 / 16 / 32 give 5.49 / 5.29 / 5.73 / 6.07 ms of GEMM + conv
-  // per 2-row forward, profiles/r04_ring_slice_length.log: shorter slices pay more reducer traffic than their parallelism buys)
-  static int slice_kt = 0;
-  if (slice_kt == 0) { const char* e = getenv("IDF_RING_SLICE_KT"); slice_kt = e ? atoi(e) : 8; if (slice_kt < 1) slice_kt = 8; }
-  if (batch == 1 && p.ws && !(p.epi & IDF_EPI_GEGLU) && tiles * 2 <= slots && nk >= 2 * slice_kt) {
-    int want = slots / tiles;
-    if (want > nk / slice_kt) want = nk / slice_kt;
+  // split-K towards one workgroup per CU (this kernel's occupancy), slices of >= RING_SLICE_KT K-tiles (two to three trips to
+  // memory with the ring's depth) plus the reducer
+  int want = 1;
+  if (batch == 1 && p.ws && !(p.epi & IDF_EPI_GEGLU) && tiles * 2 <= slots && nk >= 2 * RING_SLICE_KT) {
+    want = slots / tiles;
+    if (want > nk / RING_SLICE_KT) want = nk / RING_SLICE_KT;
     if (want > 64) want = 64;
-    while (want > 1 && (size_t)want * p.M * p.N * sizeof(float) > p.ws_bytes) --want;
-    if (want > 1) {
-      q.kt_per_slice = (nk + want - 1) / want;
-      q.splitk = (nk + q.kt_per_slice - 1) / q.kt_per_slice;
-    }
   }
-  dim3 grid(tiles, 1, q.splitk > 1 ? q.splitk : batch);
-  hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, q);
-  ++idf_stat_ring_launches;
-  if (q.splitk > 1) {
-    const size_t n8 = (size_t)q.M * ((q.N + 7) / 8);
-    hipLaunchKernelGGL(splitk_reduce_kernel<DT>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, q);
-  }
-  return idf_launch_status();
+  return launch_kloop<DT, BM, BN, gemm_kernel_ring<DT, BM, BN, WM, WN, CONV, NS>, dma_lds_bytes<BM, BN, WM, WN>(NS)>(
+      p, batch, want, s, &idf_stat_ring_launches);
 }
 
 template <int DT, bool CONV>
@@ -851,10 +597,8 @@ int launch(const CoreParams& p, int batch, hipStream_t s, int* parts_out = nullp
   // tile choice: 128x128 when N fills it; 128(M) x 64(N) for N = 64 mod 128 (e.g. 320) or small N.  For the conv
   // (long K = 9*Cin) the denser 64x64 wave tile wins even with a half-empty last column tile at Cout = 320
   // (measured +15..18 %: 512 -> 602 and 596 -> 677 TF); for the short-K dense GEMMs it loses (378 -> 352 TF).
-  // IDF_TILE_WIDE=0/1 forces the choice for A/B runs.
-  static int wide = -2;
-  if (wide == -2) { const char* e = getenv("IDF_TILE_WIDE"); wide = e ? (e[0] == '1' ? 1 : 0) : -1; }
-  const bool use_wide = (wide >= 0) ? (wide == 1) : CONV;
+  // (128 x 128 tiles for the dense N = 320 GEMMs too: measured, not shipped -- profiles/r04_tile_wide_n320.log)
+  constexpr bool use_wide = CONV;
   // K-loop variant 4 (gemm_big.hip): persistent 256 x {320,256} tiles.  IDF_GEMM_BIG=0 off, 1 auto (shape + tile
   // quantisation heuristic), 2 forced whenever the shape qualifies.
   const int big = gemm_big_mode();
@@ -873,8 +617,7 @@ int launch(const CoreParams& p, int batch, hipStream_t s, int* parts_out = nullp
       if (rc == 0 && splitk > 1) {
         CoreParams q = p;
         q.splitk = splitk; q.tail_m0 = tail_m0; q.tail_rows = p.M - tail_m0;
-        const size_t n8 = (size_t)q.tail_rows * ((q.N + 7) / 8);
-        hipLaunchKernelGGL(splitk_reduce_kernel<DT>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, q);
+        launch_reduce<DT>(q, s);
         return idf_launch_status();
       }
       return rc;
@@ -899,6 +642,14 @@ int launch(const CoreParams& p, int batch, hipStream_t s, int* parts_out = nullp
   }
   if (t128) return launch_cfg<DT, 128, 128, 64, 64, CONV>(q, batch, s);
   return launch_cfg<DT, 128, 64, 64, 32, CONV>(q, batch, s);
+}
+
+// the one place a run-time dtype picks the instantiation
+template <bool CONV>
+int launch_dt(int dtype, const CoreParams& p, int batch, hipStream_t s, int* parts_out = nullptr, int* gst_out = nullptr) {
+  if (dtype == IDF_BF16) return launch<IDF_BF16, CONV>(p, batch, s, parts_out, gst_out);
+  if (dtype == IDF_F16) return launch<IDF_F16, CONV>(p, batch, s, parts_out, gst_out);
+  return IDF_E_UNSUPPORTED;
 }
 
 }  // namespace
@@ -1058,8 +809,7 @@ extern "C" int idf_gemm(const idf_gemm_args* a, void* stream) {
     }
     CoreParams p1 = p;                                          // q | k: the first vt_col0 columns
     p1.vt_out = nullptr; p1.vt_col0 = 0; p1.N = a->vt_col0; p1.n_valid = a->vt_col0;
-    if (a->dtype == IDF_BF16) rc = launch<IDF_BF16, false>(p1, 1, s);
-    else if (a->dtype == IDF_F16) rc = launch<IDF_F16, false>(p1, 1, s);
+    rc = launch_dt<false>(a->dtype, p1, 1, s);
     if (rc) return rc;
     CoreParams p2{};                                            // V^T[Nv, M] = Wv[Nv, K] . A[M, K]^T
     p2.A = p.W + (size_t)a->vt_col0 * p.ldw; p2.lda = p.ldw; p2.M = Nv; p2.K = a->K;
@@ -1072,9 +822,7 @@ extern "C" int idf_gemm(const idf_gemm_args* a, void* stream) {
       p2.ln_stats = self_ln ? a->ln_stats_out : a->ln_stats; p2.stride_ln_stats = 0;
       p2.ln_c = a->ln_c + a->vt_col0; p2.ln_d = a->bias + a->vt_col0;
     }
-    if (a->dtype == IDF_BF16) return launch<IDF_BF16, false>(p2, 1, s);
-    if (a->dtype == IDF_F16) return launch<IDF_F16, false>(p2, 1, s);
-    return IDF_E_UNSUPPORTED;
+    return launch_dt<false>(a->dtype, p2, 1, s);
   }
   // out_stats: the persistent kernel leaves per-wave (mean, M2) partials of its output rows in the head of the workspace
   // (when it takes the launch, unsplit) and a 16-B-per-row finalize pass merges them; otherwise the statistics pass re-reads
@@ -1093,8 +841,7 @@ extern "C" int idf_gemm(const idf_gemm_args* a, void* stream) {
     if (r != IDF_BIG_UNSUPPORTED) { if (r == 0) { ++idf_stat_big_launches; ++idf_stat_projw_launches; } return r; }
   }
   if (a->out_stats && batch == 1 && p.ws) p.stat_parts = p.ws;
-  if (a->dtype == IDF_BF16) rc = launch<IDF_BF16, false>(p, batch, s, &parts);
-  else if (a->dtype == IDF_F16) rc = launch<IDF_F16, false>(p, batch, s, &parts);
+  rc = launch_dt<false>(a->dtype, p, batch, s, &parts);
   if (rc == 0 && a->out_stats) {
     if (parts > 0) rc = idf_stats_finalize(p.stat_parts, parts, a->N / parts, a->out_stats, a->M, a->out_stats_eps, s);
     else rc = idf_row_stats(a->out, a->ldo, a->out_stats, batch * a->M, a->N, a->out_stats_eps, a->dtype, stream);
@@ -1133,9 +880,8 @@ static int conv3x3_launch(const idf_conv3x3_args* a, int pad_lo, void* stream) {
     if (((uintptr_t)a->gn_partial) & 7u) return IDF_E_ALIGN;
     p.gn_partial = a->gn_partial; p.gn_hw = hw;
   }
-  int gst = 0, rc = IDF_E_UNSUPPORTED;
-  if (a->dtype == IDF_BF16) rc = launch<IDF_BF16, true>(p, 1, s, nullptr, &gst);
-  else if (a->dtype == IDF_F16) rc = launch<IDF_F16, true>(p, 1, s, nullptr, &gst);
+  int gst = 0;
+  int rc = launch_dt<true>(a->dtype, p, 1, s, nullptr, &gst);
   // the contract holds whichever kernel took the launch: where the epilogue did not leave the partials, the statistics pass does
   if (rc == 0 && gst) ++idf_stat_gn_epi_launches;
   if (rc == 0 && a->gn_partial && !gst)

@@ -1,5 +1,7 @@
 // gemm_core.h -- pieces shared by the MFMA GEMM / implicit-GEMM conv translation units (gemm_conv.hip, gemm_big.hip):
-// the launch parameter block, the K-tile depth and the 8-column epilogue.
+// the launch parameter block, the K-tile depth, the device pieces every K-loop kernel of the family uses unchanged (tile order and
+// decode, conv gather rules, LDS-DMA source rows, the fragment-read + MFMA body of a K-tile) and the 8-column epilogue.  The
+// schedules -- each kernel's order of loads, waits, barriers and computes -- stay in the kernels' own files.
 #pragma once
 #include "common.h"
 #include <atomic>
@@ -46,6 +48,124 @@ struct CoreParams {
 };
 
 constexpr int BK = 64;
+
+// ================================================================================================================
+// K-loop core.  Everything is __forceinline__ with its sizes as template parameters or arguments that are constants at the call
+// site, so it folds into the calling kernel exactly as the code it replaced (profiles/gemm_shared_core.md).
+// ================================================================================================================
+// XCD-aware tile order: workgroup L of T runs on XCD L % 8 (8 private L2s); give each XCD a CONTIGUOUS chunk of the n-fastest
+// tile list so the n-tiles that share one activation m-tile hit the same L2 (bijective for any count).
+__device__ __forceinline__ int xcd_tile(int L, int T) {
+  const int q = T >> 3, r = T & 7, xcd = L & 7, i = L >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
+}
+// tile of the n-fastest list -> its origin, the operands of its batch entry (blockIdx.z; split-K launches are never batched) and
+// the K-tiles [kt_begin, kt_begin + nk) of this block's K-slice (blockIdx.z of a split-K launch).  Filled through the reference:
+// returned by value, gemm_kernel_ring's kernel-argument loads come out in another order.
+struct TileSlice { int m0, n0, bz; const unsigned short* Wb; const unsigned short* Ab; int kt_begin, nk; };
+template <int BM, int BN>
+__device__ __forceinline__ void tile_slice(const CoreParams& p, int tile, TileSlice& t) {
+  const int tiles_n = (p.N + BN - 1) / BN;
+  const int m_tile = tile / tiles_n;
+  t.n0 = (tile - m_tile * tiles_n) * BN, t.m0 = m_tile * BM;
+  t.bz = (p.splitk > 1) ? 0 : blockIdx.z;
+  t.Wb = p.W + (size_t)t.bz * p.strideW;
+  t.Ab = p.A + (size_t)t.bz * p.strideA;
+  const int nk_all = p.K / BK;
+  t.kt_begin = (p.splitk > 1) ? blockIdx.z * p.kt_per_slice : 0;
+  t.nk = (p.splitk > 1) ? min(p.kt_per_slice, nk_all - t.kt_begin) : nk_all;
+}
+
+// ---- conv gather.  Output row m = (sample b, output pixel yo, xo); its 3x3 window starts at (ay, ax) of the (upsampled) image
+struct ConvPixel { int b, yo, xo; };
+__device__ __forceinline__ ConvPixel conv_pixel(const CoreParams& p, int m) {
+  const int hw = p.Ho * p.Wo;
+  const int b = m / hw, rem = m - b * hw;
+  const int yo = rem / p.Wo;
+  return {b, yo, rem - yo * p.Wo};
+}
+// window origin of row m (pre-multiplied by stride, minus the leading pad); returns the element offset of the row's image
+__device__ __forceinline__ size_t conv_row_origin(const CoreParams& p, int m, int& ay, int& ax) {
+  const ConvPixel px = conv_pixel(p, m);
+  ay = px.yo * p.stride - p.pad_lo;
+  ax = px.xo * p.stride - p.pad_lo;
+  return (size_t)px.b * p.Hin * p.Win * p.lda;
+}
+// K element k_elem -> (3x3 tap, first input channel); the step to the next K-tile of `bk` elements; is pixel (yi, xi) of the tap
+// inside the Hup x Wup image (else it is zero padding)
+__device__ __forceinline__ void conv_tap_at(const CoreParams& p, int k_elem, int& tap, int& ci0) {
+  tap = k_elem / p.Cin;
+  ci0 = k_elem - tap * p.Cin;
+}
+__device__ __forceinline__ void conv_tap_step(const CoreParams& p, int bk, int& tap, int& ci0) {
+  ci0 += bk;
+  if (ci0 >= p.Cin) { ci0 = 0; ++tap; }
+}
+__device__ __forceinline__ bool conv_tap_inside(int yi, int xi, int Hup, int Wup) { return (yi >= 0) & (yi < Hup) & (xi >= 0) & (xi < Wup); }
+
+// ---- LDS-DMA tile image of the 4-wave kernels: linear 128-B rows (64 elements); instruction j of a wave covers tile rows
+// 8 * (wave + 4 j) .. + 7, lane -> (row lane >> 3, 16-B slot lane & 7); the slot is XOR-swizzled on the SOURCE side (slot c of LDS
+// row `row` holds global chunk c ^ ((row >> 1) & 7)) and, identically, on the fragment reads (ktile_mfma): conflict-free ds_read_b128
+__device__ __forceinline__ int dma_row(int wave, int j, int lane) { return 8 * (wave + 4 * j) + (lane >> 3); }
+__device__ __forceinline__ int dma_chunk(int row, int lane) { return ((lane & 7) ^ ((row >> 1) & 7)) * 8; }
+// per-lane source of instruction j of a dense operand tile: rows r0 .. of the [rows][ld] matrix `base` (rows beyond the matrix
+// are clamped duplicates), from element k0 of the row
+__device__ __forceinline__ const unsigned short* dma_src_row(const unsigned short* base, int ld, int r0, int rows, size_t k0, int wave,
+                                                             int j, int lane) {
+  const int row = dma_row(wave, j, lane);
+  const int n = min(r0 + row, rows - 1);
+  return base + (size_t)n * ld + k0 + dma_chunk(row, lane);
+}
+// ... and of all INST instructions of the tile (gemm_kernel_dma calls dma_src_row from its own loop: through this form its
+// register allocation moves, 123 -> 108 and 63 -> 68 VGPRs)
+template <int INST>
+__device__ __forceinline__ void dma_src_rows(const unsigned short* (&src)[INST], const unsigned short* base, int ld, int r0, int rows,
+                                             size_t k0, int wave, int lane) {
+#pragma unroll
+  for (int j = 0; j < INST; ++j) src[j] = dma_src_row(base, ld, r0, rows, k0, wave, j, lane);
+}
+
+template <int TN, int TM>
+__device__ __forceinline__ void clear_acc(f32x16 (&acc)[TN][TM]) {
+#pragma unroll
+  for (int a = 0; a < TN; ++a)
+#pragma unroll
+    for (int b = 0; b < TM; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+}
+// One K-tile: acc[a][b] += W fragment a . A fragment b over the BK / 16 K-steps.  wf_base / af_base = the lane's row (l31) of the
+// wave's weight / activation rows in the LDS image of row stride RS elements; hi = lane >> 5 selects the 16-B half of a K-step;
+// SWZ: the 16-B slot is XOR-swizzled with f_sw = (l31 >> 1) & 7 (fragment rows are (multiple of 32) + l31).
+// The fragment reads of K-step ks+1 are issued BEFORE the MFMAs of K-step ks (register double-buffer), so the LDS latency (~100+
+// cycles) hides under 4-8 MFMAs instead of stalling every K-step (the compiler does not do this).
+template <int DT, int TN, int TM, int RS, bool SWZ>
+__device__ __forceinline__ void ktile_mfma(f32x16 (&acc)[TN][TM], const unsigned short* wf_base, const unsigned short* af_base, int hi,
+                                           int f_sw) {
+  u32x4 wf[2][TN], af[2][TM];
+  {
+    const int slot = SWZ ? (hi ^ f_sw) * 8 : hi * 8;
+#pragma unroll
+    for (int a = 0; a < TN; ++a) wf[0][a] = *reinterpret_cast<const u32x4*>(wf_base + a * 32 * RS + slot);
+#pragma unroll
+    for (int b = 0; b < TM; ++b) af[0][b] = *reinterpret_cast<const u32x4*>(af_base + b * 32 * RS + slot);
+  }
+#pragma unroll
+  for (int ks = 0; ks < BK / 16; ++ks) {
+    const int cur = ks & 1, nxt = cur ^ 1;
+    if (ks + 1 < BK / 16) {
+      const int slot = SWZ ? (((ks + 1) * 2 + hi) ^ f_sw) * 8 : (ks + 1) * 16 + hi * 8;
+#pragma unroll
+      for (int a = 0; a < TN; ++a) wf[nxt][a] = *reinterpret_cast<const u32x4*>(wf_base + a * 32 * RS + slot);
+#pragma unroll
+      for (int b = 0; b < TM; ++b) af[nxt][b] = *reinterpret_cast<const u32x4*>(af_base + b * 32 * RS + slot);
+    }
+#pragma unroll
+    for (int a = 0; a < TN; ++a)
+#pragma unroll
+      for (int b = 0; b < TM; ++b) acc[a][b] = Elem<DT>::mfma32(wf[cur][a], af[cur][b], acc[a][b]);
+  }
+}
 
 // Epilogue for 8 consecutive output columns n..n+7 of row m (n % 8 == 0).  Shared by the main kernel (after the
 // accumulators were transposed through LDS so that a lane owns a contiguous 8-column run -> 16-B coalesced residual /
@@ -138,7 +258,6 @@ __device__ __forceinline__ void epilogue8(const CoreParams& p, int bz, int m, in
     }
   }
 }
-
 
 }  // namespace idfcore
 

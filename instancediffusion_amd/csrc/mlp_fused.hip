@@ -54,12 +54,6 @@ struct MlpParams {
   int M;
 };
 
-// LDS-DMA as inline assembly (see gemm_big.hip): lds = LDS byte address of lane 0's 16-B slot, through M0
-__device__ __forceinline__ void mlp_dma16(const void* sbase /* wave-uniform */, unsigned voff_bytes, unsigned lds) {
-  lds = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(voff_bytes), "s"(sbase) : "memory");
-}
-
 // Schedule details, each measured on its own in profiles/r04_mlp_variants.log (all variants bit-identical):
 //   * skewed fill (as in gemm_big.hip): an LDS-DMA piece holds the issuing wave ~60 cycles, 7-8 pieces per wave and chunk; the
 //     older waves 0-3 enqueue right behind the chunk's barrier, the younger waves 4-7 one piece per two MFMAs of their first
@@ -123,12 +117,12 @@ __global__ __launch_bounds__(512, 2) void mlp320_kernel(const MlpParams p, const
   auto issue_piece = [&](int idx, int j, int slot) {
     char* const base = smem + slot * SLOT_BYTES;
     if (idx == 0) {
-      if (wave == 7) mlp_dma16(p.cd + (size_t)j * 128, (unsigned)((lane & 31) * 16), lds_u32(base + W1_BYTES + W2_BYTES));
+      if (wave == 7) dma16_sv(p.cd + (size_t)j * 128, (unsigned)((lane & 31) * 16), lds_u32(base + W1_BYTES + W2_BYTES));
     } else if (idx < 6) {
-      mlp_dma16(p.w1 + (size_t)j * 64 * p.ldw1 + (idx - 1) * 64, w1_voff, lds_u32(base + (idx - 1) * 8192 + wave * 1024));
+      dma16_sv(p.w1 + (size_t)j * 64 * p.ldw1 + (idx - 1) * 64, w1_voff, lds_u32(base + (idx - 1) * 8192 + wave * 1024));
     } else {
       const int t = idx - 6;
-      if (wave + 8 * t < 20) mlp_dma16(p.w2p + j * 32, w2_voff[t], lds_u32(base + W1_BYTES + (wave + 8 * t) * 1024));
+      if (wave + 8 * t < 20) dma16_sv(p.w2p + j * 32, w2_voff[t], lds_u32(base + W1_BYTES + (wave + 8 * t) * 1024));
     }
   };
   auto issue_chunk = [&](int j, int slot) {
@@ -468,9 +462,9 @@ __global__ __launch_bounds__(256, 1) void mlp320w_kernel(const MlpParams p, cons
       for (int kt = 0; kt < 5; ++kt)
 #pragma unroll
         for (int u = 0; u < 2; ++u)
-          mlp_dma16(w1g + (size_t)ch * w1_chunk + u * c.w1_ustride + kt * 128, c.w1_voff,
+          dma16_sv(w1g + (size_t)ch * w1_chunk + u * c.w1_ustride + kt * 128, c.w1_voff,
                     smem_lds + (unsigned)(ch * SLOT_BYTES + wave * 1024 + kt * 8192 + u * 4096));
-    if (wave == 3) mlp_dma16(cdg, c.cd_voff, smem_lds + (unsigned)(W1_BYTES + W2_BYTES));
+    if (wave == 3) dma16_sv(cdg, c.cd_voff, smem_lds + (unsigned)(W1_BYTES + W2_BYTES));
   }
 
   f32x16 acc1[2][2];

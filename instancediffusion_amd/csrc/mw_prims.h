@@ -187,11 +187,6 @@ __device__ __forceinline__ void mw_swap32(unsigned& x, unsigned& y) { asm volati
 __device__ __forceinline__ void mw_store128(unsigned voff, const u32x4& v, const void* sbase) {
   asm volatile("global_store_dwordx4 %0, %1, %2" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
 }
-// one LDS-DMA piece with run-time addresses (prologues): lds = LDS byte address of lane 0's 16-B slot (uniform), through M0
-__device__ __forceinline__ void mw_dma_rt(const void* sbase /* uniform */, unsigned voff, unsigned lds) {
-  lds = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(voff), "s"(sbase) : "memory");
-}
 template <int N> __device__ __forceinline__ void mw_wait_vm_barrier() { asm volatile("s_waitcnt vmcnt(%c0)\n\ts_barrier" ::"n"(N) : "memory"); }
 
 }  // namespace idfmw

@@ -89,7 +89,7 @@ struct Row640 {
       reinterpret_cast<f32x4*>(smem + R640_CD_OFF + N * 4)[i] = reinterpret_cast<const f32x4*>(dd)[i];
     }
 #pragma unroll
-    for (int kt = 0; kt < 10; ++kt) mw_dma_rt(c.wb + kt * 128, w1_voff, smem_lds + (unsigned)(r.wave * 1024 + kt * 4096));
+    for (int kt = 0; kt < 10; ++kt) dma16_sv(c.wb + kt * 128, w1_voff, smem_lds + (unsigned)(r.wave * 1024 + kt * 4096));
     {
       const unsigned short* xr = row_ptr(tile);
       mw_static_for<40>([&](auto kc) { mw_load_x2<decltype(kc)::value, decltype(kc)::value>(xr); });

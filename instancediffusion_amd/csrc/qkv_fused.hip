@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256, 1) void qkv320w_kernel(const QwParams p, const
   for (int kt = 0; kt < 5; ++kt)
 #pragma unroll
     for (int u = 0; u < 2; ++u)
-      mw_dma_rt(c.w1b[u] + kt * 128, w1_voff, smem_lds + (unsigned)(wave * 1024 + kt * 8192 + u * 4096));
+      dma16_sv(c.w1b[u] + kt * 128, w1_voff, smem_lds + (unsigned)(wave * 1024 + kt * 8192 + u * 4096));
   auto row_ptr = [&](int t, int rg) { return p.x + (size_t)(t * QW_BM + wave * 64 + rg * 32 + l31) * p.ldx + 8 * hi; };
   auto st_ptr = [&](int t) { return p.ln_stats + 2 * (size_t)(t * QW_BM + wave * 64 + l31); };
   {

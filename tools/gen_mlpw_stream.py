@@ -122,10 +122,10 @@ def dma_pieces():
         return ps
     for kt in range(5):
         for u in range(2):
-            ps.append(f"mlp_dma16(c.w1src + {u} * c.w1_ustride + {kt * 128}, c.w1_voff, c.w1dst + {kt * 8192 + u * 4096});")
+            ps.append(f"dma16_sv(c.w1src + {u} * c.w1_ustride + {kt * 128}, c.w1_voff, c.w1dst + {kt * 8192 + u * 4096});")
     for t in range(5):
-        ps.append(f"mlp_dma16(c.w2src + {t} * c.w2_tstride, c.w2_voff, c.w2dst + {t * 4096});")
-    ps.append("if (c.wave == 3) mlp_dma16(c.cdsrc, c.cd_voff, c.cddst);")
+        ps.append(f"dma16_sv(c.w2src + {t} * c.w2_tstride, c.w2_voff, c.w2dst + {t * 4096});")
+    ps.append("if (c.wave == 3) dma16_sv(c.cdsrc, c.cd_voff, c.cddst);")
     return ps
 
 
