@@ -331,6 +331,30 @@ int idf_plms_update(const float* x, const float* e_t, const float* e1, const flo
                     const float* e_next, int mode, float a_t, float a_prev, float sqrt_1m_at,
                     float* x_out, long long n, void* stream);
 
+/* ---- DDIM sampler: the per-step arithmetic around the UNet forward (ddim.py:94-98, :110-131; ldm.py:17-20) ----------------------
+ * Both entry points were added within ABI 5: new symbols only, no struct or existing entry point changed.  Both evaluate torch's
+ * fp32 expression with torch's operations in torch's order, every operation rounded to fp32 on its own (nothing is contracted into
+ * an FMA, the division is the correctly rounded one): the result equals the reference's tensor expression bit for bit.  No
+ * synchronisation, no allocation; hipGraph-capturable.  16-B accesses where every pointer is 16-B aligned and the vectors are
+ * whole, scalar accesses otherwise (decided per launch).
+ * idf_ddim_update = p_sample_ddim behind the model calls (ddim.py:110-131), one launch instead of idf_cfg_combine + an update:
+ *   e       = eps_uncond + guidance * (eps_cond - eps_uncond)           (:114; eps_uncond == NULL: e = eps_cond, guidance unused)
+ *   pred_x0 = (x - sqrt_1m_at * e) / sqrt(a_t)                          (:124)
+ *   x_prev  = sqrt(a_prev) * pred_x0 + sqrt(1 - a_prev - sigma_t^2) * e (:127, :129)  [+ sigma_t * noise when noise != NULL (:128)]
+ *   The three square roots are taken by the launcher in fp32, each operation rounded on its own, as the reference's
+ *   torch.full(...) tensors are (:118-127).  eps_cond / eps_uncond: the two halves of the engine's [cond | uncond] eps buffer.
+ *   x_prev may alias x; pred_x0 may be NULL (not stored).  IDF_E_ARG before any launch: a null x / eps_cond / x_prev, n < 1,
+ *   a_t <= 0, a_prev < 0, sigma_t < 0, (1 - a_prev) - sigma_t^2 < 0, sigma_t != 0 with noise == NULL.
+ * idf_q_sample_blend = q_sample (ldm.py:17-20) and the inpainting blend in front of a step (ddim.py:94-98; plms.py:99-104):
+ *   out = (sqrt_ac * x0 + sqrt_1m_ac * noise) * mask + (1 - mask) * img
+ *   x0, noise, img, out: [B][C][HW] fp32; mask: [B][1][HW] (mask_channels 1, broadcast over the channels) or [B][C][HW]
+ *   (mask_channels C).  out may alias img.  IDF_E_ARG before any launch: a null pointer, B / C / HW < 1, mask_channels not 1 or C. */
+int idf_ddim_update(const float* x, const float* eps_cond, const float* eps_uncond /* NULL = unguided */, float guidance,
+                    float a_t, float a_prev, float sigma_t, float sqrt_1m_at, const float* noise /* NULL iff sigma_t == 0 */,
+                    float* x_prev, float* pred_x0 /* or NULL */, long long n, void* stream);
+int idf_q_sample_blend(const float* x0, const float* noise, const float* mask, const float* img, float sqrt_ac, float sqrt_1m_ac,
+                       float* out, int B, int C, long long HW, int mask_channels /* 1 or C */, void* stream);
+
 /* ---- Multi-instance Sampler merge (plms_instance.py:112-135) ---------------------------------------------
  * lat: [n_inst+1][B][C][H][W] fp32.  mode 0: mean over the first dim; mode 1: crop-and-paste of instance j's
  * latent box (boxes: int32 [n_inst][4] = int(box*latent_size), reference index order dim2<-x, dim3<-y).      */

@@ -6,6 +6,10 @@ caption}]) and the same call sequence as the reference (inference.py:165-309): d
 ``utils.input.prepare_batch`` (+ ``prepare_instance_meta`` per instance when MIS is on) -> ``PLMSSampler`` /
 ``PLMSSamplerInst`` -> ``autoencoder.decode`` -> PNGs.  UNet, samplers and VAE decoder run on the HIP engine.
 
+Beyond the reference's flags: ``--sampler ddim`` (+ ``--ddim_eta``) runs ``DDIMSampler`` (ldm/models/diffusion/ddim.py) instead of
+``PLMSSampler``, and ``--init_image`` / ``--inpaint_mask`` reach the samplers' ``mask`` / ``x0`` arguments (plms.py:99-104,
+ddim.py:94-98): the image is encoded by ``AutoencoderKL.encode``, the mask is pooled to the latent grid.
+
 Two neighbours of the path need assets that do not exist offline; both are handled explicitly, never silently:
   * text encoding (CLIP-L/14: ``ldm/modules/encoders``, ``utils/model.py:12-18``): with ``--ckpt`` the checkpoint's
     text encoder is used (needs the BPE vocabulary locally, see host/text_encoder.py); ``--text_encoder synthetic``
@@ -27,7 +31,7 @@ import torch
 from instancediffusion_amd.host.alpha import alpha_generator, set_alpha_scale
 from instancediffusion_amd.host.config import instantiate_from_config, load_yaml
 from instancediffusion_amd.host.input import meta_from_demo_json, prepare_batch, prepare_instance_meta
-from instancediffusion_amd.host.samplers import PLMSSampler, PLMSSamplerInst
+from instancediffusion_amd.host.samplers import DDIMSampler, PLMSSampler, PLMSSamplerInst
 
 MAX_OBJS = 30
 
@@ -89,6 +93,30 @@ def save_images(images: torch.Tensor, folder: str) -> list:
     return names
 
 
+def _open_sized(path: str, size: int, mode: str):
+    from PIL import Image
+    img = Image.open(path).convert(mode)
+    if img.size != (size, size):
+        raise SystemExit(f"{path} is {img.size[0]} x {img.size[1]}: the model samples {size} x {size} images (8 x its latent size)")
+    return img
+
+
+def load_init_image(path: str, size: int) -> torch.Tensor:
+    """``--init_image``: an RGB image of size x size -> fp32 [1, 3, size, size] in [-1, 1] (v / 127.5 - 1), the encoder's input."""
+    import numpy as np
+    arr = np.asarray(_open_sized(path, size, "RGB"), dtype=np.float32)
+    return (torch.from_numpy(arr.copy()).permute(2, 0, 1) / 127.5 - 1.0).unsqueeze(0).contiguous()
+
+
+def latent_mask(path: str, size: int) -> torch.Tensor:
+    """``--inpaint_mask``: a grey-scale image of size x size, a pixel >= 128 means "keep the original" -> fp32 [1, 1, size / 8,
+    size / 8] of {0, 1}: a latent pixel keeps the original only if all of its 8 x 8 pixels do (min-pool), so that nothing the user
+    asked to repaint is held to the original."""
+    import numpy as np
+    keep = torch.from_numpy((np.asarray(_open_sized(path, size, "L")) >= 128).astype(np.float32))
+    return -torch.nn.functional.max_pool2d(-keep[None, None], 8)
+
+
 def clip_scores(args, images: torch.Tensor, data: dict, dtype) -> dict:
     """``--clip_score``: the local CLIP score (host/clip_score.py) of every instance of every decoded image, straight from the fp32
     decoder output -- on backend ``hip`` the pixels never leave the device (``idf_clip_crop_resize`` quantises them as
@@ -139,7 +167,25 @@ def main():
                          "and no path, a key-seeded synthetic CLIP model")
     ap.add_argument("--keep_best", type=int, default=None,
                     help="write only the K images with the best mean CLIP score (needs --clip_score; the JSON still lists all)")
+    ap.add_argument("--sampler", choices=["plms", "ddim"], default="plms",
+                    help="ddim: DDIMSampler (ldm/models/diffusion/ddim.py) instead of PLMSSampler; without the Multi-instance Sampler")
+    ap.add_argument("--ddim_eta", type=float, default=None,
+                    help="--sampler ddim: eta of the DDIM variance schedule (default 0: deterministic; 1: DDPM-like)")
+    ap.add_argument("--init_image", type=str, default=None,
+                    help="inpainting: PNG of the sampled size whose kept region is held to the original (needs --inpaint_mask)")
+    ap.add_argument("--inpaint_mask", type=str, default=None,
+                    help="inpainting: grey-scale PNG of the sampled size, >= 128 keeps the original, < 128 is repainted")
     args = ap.parse_args()
+    if args.sampler == "ddim" and args.mis > 0:
+        raise SystemExit("--sampler ddim has no Multi-instance Sampler (the reference has none): give --mis 0")
+    if args.ddim_eta is not None and args.sampler != "ddim":
+        raise SystemExit("--ddim_eta needs --sampler ddim")
+    if args.ddim_eta is not None and args.ddim_eta < 0:
+        raise SystemExit("--ddim_eta must be >= 0")
+    if (args.init_image is None) != (args.inpaint_mask is None):
+        raise SystemExit("inpainting needs both --init_image and --inpaint_mask")
+    if args.init_image is not None and args.mis > 0:
+        raise SystemExit("inpainting (--init_image / --inpaint_mask) runs without the Multi-instance Sampler: give --mis 0")
     if args.keep_best is not None and (args.clip_score is None or args.keep_best < 1):
         raise SystemExit("--keep_best K needs --clip_score and K >= 1")
     if args.clip_score and not (args.clip_path or args.synthetic_weights):
@@ -189,6 +235,13 @@ def main():
     meta = meta_from_demo_json(data, args.alpha, ckpt=args.ckpt, save_folder_name=save_folder_name)
     torch.manual_seed(args.seed)
     starting_noise = torch.randn(args.num_images, 4, model.image_size, model.image_size).to(dev)
+    inpaint = {}
+    if args.init_image is not None:
+        size = 8 * model.image_size
+        image, keep = load_init_image(args.init_image, size), latent_mask(args.inpaint_mask, size)
+        # the posterior sample times scale_factor (autoencoder.py:27-31), its noise the next draw of the CPU default generator
+        x0 = autoencoder.encode(image.to(dev))
+        inpaint = dict(mask=keep.to(dev).expand(args.num_images, -1, -1, -1), x0=x0.expand(args.num_images, -1, -1, -1))
 
     inp, uc = get_model_inputs(meta, gi, text_encoder, phrase_encoder, args.num_images, dev, starting_noise,
                                args.negative_prompt, use_masked_att=args.use_masked_att)
@@ -203,8 +256,12 @@ def main():
             inputs.append(inst)
         samples = sampler.sample(S=args.steps, shape=shape, input=inputs, uc=uc, guidance_scale=args.guidance_scale)
     else:
-        sampler = PLMSSampler(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale)
-        samples = sampler.sample(S=args.steps, shape=shape, input=inp, uc=uc, guidance_scale=args.guidance_scale)
+        if args.sampler == "ddim":
+            sampler = DDIMSampler(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale)
+            inpaint["eta"] = args.ddim_eta or 0.
+        else:
+            sampler = PLMSSampler(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale)
+        samples = sampler.sample(S=args.steps, shape=shape, input=inp, uc=uc, guidance_scale=args.guidance_scale, **inpaint)
     images = autoencoder.decode(samples)                                   # inference.py:95
     folder = os.path.join(args.output, save_folder_name)
     report = None

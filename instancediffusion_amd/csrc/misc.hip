@@ -1,5 +1,6 @@
 // misc.hip -- small latency-bound kernels of the sampling path (gfx950): timestep embedding, UniFusion token-MLP
-// input builder, first conv from the fp32 NCHW latent, fused CFG / PLMS update, Multi-instance-Sampler merge.
+// input builder, first conv from the fp32 NCHW latent, fused CFG / PLMS update, fused DDIM step and q_sample blend,
+// Multi-instance-Sampler merge.
 #include "common.h"
 
 namespace {
@@ -259,6 +260,85 @@ __global__ void plms_kernel(const float* __restrict__ x, const float* __restrict
   xo[i] = sqrt_aprev * pred_x0 + sqrt_1m_aprev * ep;
 }
 
+// ddim.py:110-131 in one launch: guidance, pred_x0, dir_xt, the noise term.  Every operation is rounded to fp32 on its own, in the
+// reference's order (no contraction: a product that fed an FMA would skip its rounding), so the result is torch's fp32 expression
+// bit for bit.  eu == nullptr: unguided (e = ec); nz == nullptr: no noise term; p0 == nullptr: pred_x0 is not stored.
+// xo may alias x (no __restrict__ on either): a thread reads its own elements before it writes them.
+__device__ __forceinline__ void ddim_elem(float x, float ec, float eu, bool guided, float g, float s1m, float sqrt_at, float sqrt_aprev,
+                                          float dc, float sigma, float nz, bool noisy, float& r, float& p) {
+#pragma clang fp contract(off)
+  float e = ec;
+  if (guided) { const float d = ec - eu; const float m = g * d; e = eu + m; }          // :114
+  const float t = s1m * e;
+  p = (x - t) / sqrt_at;                                                              // :124
+  const float a = sqrt_aprev * p;
+  const float b = dc * e;                                                             // :127
+  r = a + b;
+  if (noisy) { const float s = sigma * nz; r = r + s; }                               // :128-129
+}
+
+template <int V>
+__global__ void ddim_kernel(const float* x, const float* __restrict__ ec, const float* __restrict__ eu, float g, float s1m,
+                            float sqrt_at, float sqrt_aprev, float dc, float sigma, const float* __restrict__ nz, float* xo,
+                            float* __restrict__ p0, long long n) {
+  static_assert(V == 1 || V == 4, "scalar or 16-B accesses");
+  const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= n) return;                                                                 // V == 4: the launcher guarantees n % 4 == 0
+  if constexpr (V == 4) {
+    const f32x4 xv = *reinterpret_cast<const f32x4*>(x + i), cv = *reinterpret_cast<const f32x4*>(ec + i);
+    const f32x4 uv = eu ? *reinterpret_cast<const f32x4*>(eu + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+    const f32x4 nv = nz ? *reinterpret_cast<const f32x4*>(nz + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 rv, pv;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float r, p;
+      ddim_elem(xv[j], cv[j], uv[j], eu != nullptr, g, s1m, sqrt_at, sqrt_aprev, dc, sigma, nv[j], nz != nullptr, r, p);
+      rv[j] = r; pv[j] = p;
+    }
+    *reinterpret_cast<f32x4*>(xo + i) = rv;
+    if (p0) *reinterpret_cast<f32x4*>(p0 + i) = pv;
+  } else {
+    float r, p;
+    ddim_elem(x[i], ec[i], eu ? eu[i] : 0.f, eu != nullptr, g, s1m, sqrt_at, sqrt_aprev, dc, sigma, nz ? nz[i] : 0.f, nz != nullptr, r, p);
+    xo[i] = r;
+    if (p0) p0[i] = p;
+  }
+}
+
+// ldm.py:17-20 (q_sample) + ddim.py:94-98 (the inpainting blend) in one launch, torch's operations in torch's order, each rounded
+// on its own:  out = (sqrt_ac x0 + sqrt_1m_ac noise) mask + (1 - mask) img.  The mask is [B][1][HW] (broadcast over the channels)
+// or [B][C][HW]; out may alias img (no __restrict__ on either).
+__device__ __forceinline__ float blend_elem(float x0, float nz, float m, float img, float sa, float s1) {
+#pragma clang fp contract(off)
+  const float t1 = sa * x0;
+  const float t2 = s1 * nz;
+  const float q = t1 + t2;                                                            // ldm.py:19-20
+  const float u = q * m;
+  const float w = 1.0f - m;
+  const float v = w * img;
+  return u + v;                                                                       // ddim.py:97
+}
+
+template <int V>
+__global__ void q_sample_blend_kernel(const float* __restrict__ x0, const float* __restrict__ nz, const float* __restrict__ mask,
+                                      const float* img, float sa, float s1, float* out, long long total, long long HW,
+                                      long long CHW, bool mask_per_channel) {
+  static_assert(V == 1 || V == 4, "scalar or 16-B accesses");
+  const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= total) return;                                                             // V == 4: whole vectors, each inside one mask row
+  const long long mi = mask_per_channel ? i : (i / CHW) * HW + i % HW;
+  if constexpr (V == 4) {
+    const f32x4 xv = *reinterpret_cast<const f32x4*>(x0 + i), nv = *reinterpret_cast<const f32x4*>(nz + i);
+    const f32x4 mv = *reinterpret_cast<const f32x4*>(mask + mi), iv = *reinterpret_cast<const f32x4*>(img + i);
+    f32x4 ov;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ov[j] = blend_elem(xv[j], nv[j], mv[j], iv[j], sa, s1);
+    *reinterpret_cast<f32x4*>(out + i) = ov;
+  } else {
+    out[i] = blend_elem(x0[i], nz[i], mask[mi], img[i], sa, s1);
+  }
+}
+
 // plms_instance.py:112-135
 __global__ void mis_merge_kernel(const float* __restrict__ lat, const int* __restrict__ boxes, float* __restrict__ out,
                                  int n_inst, int B, int C, int H, int W, int mode) {
@@ -479,6 +559,45 @@ extern "C" int idf_plms_update(const float* x, const float* e_t, const float* e1
   const float sqrt_at = sqrtf(a_t), sqrt_aprev = sqrtf(a_prev), sqrt_1m_aprev = sqrtf(1.0f - a_prev);
   hipLaunchKernelGGL(plms_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, x, e_t, e1, e2, e3, e_next, mode,
                      sqrt_at, sqrt_aprev, sqrt_1m_at, sqrt_1m_aprev, x_out, n);
+  return idf_launch_status();
+}
+
+extern "C" int idf_ddim_update(const float* x, const float* eps_cond, const float* eps_uncond, float guidance, float a_t, float a_prev,
+                               float sigma_t, float sqrt_1m_at, const float* noise, float* x_prev, float* pred_x0, long long n,
+                               void* stream) {
+#pragma clang fp contract(off)
+  if (!x || !eps_cond || !x_prev || n < 1) return IDF_E_ARG;
+  if (!(a_t > 0.0f) || !(a_prev >= 0.0f) || !(sigma_t >= 0.0f)) return IDF_E_ARG;
+  if (sigma_t != 0.0f && !noise) return IDF_E_ARG;
+  // float32 host arithmetic, one rounding per operation: the reference's torch.full(...) tensors (ddim.py:118-127)
+  const float one_m = 1.0f - a_prev;
+  const float s2 = sigma_t * sigma_t;
+  const float rad = one_m - s2;
+  if (!(rad >= 0.0f)) return IDF_E_ARG;
+  const float sqrt_at = sqrtf(a_t), sqrt_aprev = sqrtf(a_prev), dc = sqrtf(rad);
+  hipStream_t s = (hipStream_t)stream;
+  const bool v4 = (n % 4) == 0 && aligned16(x) && aligned16(eps_cond) && aligned16(x_prev) && (!eps_uncond || aligned16(eps_uncond)) &&
+                  (!noise || aligned16(noise)) && (!pred_x0 || aligned16(pred_x0));
+  if (v4) hipLaunchKernelGGL(ddim_kernel<4>, grid1d(n / 4), dim3(256), 0, s, x, eps_cond, eps_uncond, guidance, sqrt_1m_at, sqrt_at,
+                             sqrt_aprev, dc, sigma_t, noise, x_prev, pred_x0, n);
+  else hipLaunchKernelGGL(ddim_kernel<1>, grid1d(n), dim3(256), 0, s, x, eps_cond, eps_uncond, guidance, sqrt_1m_at, sqrt_at,
+                          sqrt_aprev, dc, sigma_t, noise, x_prev, pred_x0, n);
+  return idf_launch_status();
+}
+
+extern "C" int idf_q_sample_blend(const float* x0, const float* noise, const float* mask, const float* img, float sqrt_ac,
+                                  float sqrt_1m_ac, float* out, int B, int C, long long HW, int mask_channels, void* stream) {
+  if (!x0 || !noise || !mask || !img || !out || B < 1 || C < 1 || HW < 1) return IDF_E_ARG;
+  if (mask_channels != 1 && mask_channels != C) return IDF_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const long long CHW = (long long)C * HW, total = (long long)B * CHW;
+  const bool per_channel = mask_channels == C;                   // C == 1: both layouts are the same tensor
+  // 16-B accesses: every pointer aligned, whole vectors, and no vector across a row of a channel-broadcast mask
+  const bool v4 = (total % 4) == 0 && (per_channel || (HW % 4) == 0) && aligned16(x0) && aligned16(noise) && aligned16(mask) && aligned16(img) && aligned16(out);
+  if (v4) hipLaunchKernelGGL(q_sample_blend_kernel<4>, grid1d(total / 4), dim3(256), 0, s, x0, noise, mask, img, sqrt_ac, sqrt_1m_ac,
+                             out, total, HW, CHW, per_channel);
+  else hipLaunchKernelGGL(q_sample_blend_kernel<1>, grid1d(total), dim3(256), 0, s, x0, noise, mask, img, sqrt_ac, sqrt_1m_ac, out,
+                          total, HW, CHW, per_channel);
   return idf_launch_status();
 }
 

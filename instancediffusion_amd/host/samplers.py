@@ -1,7 +1,7 @@
-"""PLMS sampler and the Multi-instance Sampler (MIS) for the MI355X engine.
+"""PLMS sampler, the Multi-instance Sampler (MIS) and the DDIM sampler for the MI355X engine.
 
-Host mirror of ``ldm/models/diffusion/plms.py`` (PLMSSampler) and ``plms_instance.py`` (PLMSSamplerInst): same
-constructor / ``sample()`` API, same schedule, same update rule and quirks, different execution plan:
+Host mirror of ``ldm/models/diffusion/plms.py`` (PLMSSampler), ``plms_instance.py`` (PLMSSamplerInst) and ``ddim.py``
+(DDIMSampler): same constructor / ``sample()`` API, same schedule, same update rule and quirks, different execution plan:
 
   * the conditional and unconditional (classifier-free guidance) evaluations of a step run as ONE batched UNet
     forward; in MIS phase 1 all N+1 instance trajectories (x images) advance together in one batch -- the reference
@@ -12,7 +12,9 @@ constructor / ``sample()`` API, same schedule, same update rule and quirks, diff
     (instance, image) work units, the instance latents are recombined by ONE all-gather of the unit latents each rank owns
     (scattered by index into the fixed [instance][image] stack: pure data movement) and merged by the
     same ``idf_mis_merge`` call as on one rank -- outputs are bit-identical at every world size -- and phase 2 is
-    sharded over images.
+    sharded over images;
+  * DDIM: the raw [cond | uncond] eps halves of the step's one forward go straight into ``idf_ddim_update`` (guidance, pred_x0,
+    direction and noise term in one launch), the inpainting blend in front of a step is one ``idf_q_sample_blend`` launch.
 """
 from __future__ import annotations
 
@@ -438,3 +440,84 @@ class PLMSSamplerInst(_PLMSBase):
                     out[torch.tensor(theirs, device=dev)] = recv[r][:len(theirs)]
         input_all[0]["x"] = out
         return out
+
+
+class DDIMSampler(_PLMSBase):
+    """ddim.py:7-131.  ``eta`` > 0 (stochastic sampling) and the ``mask`` / ``x0`` inpainting blend included.
+
+    Noise comes from ONE overridable attribute, ``noise_fn(shape) -> fp32 tensor on the engine's device`` (default
+    ``torch.randn``), in the reference's order within a step: the q_sample draw (ldm.py:18), then the step's (ddim.py:128).
+    Deliberate deviation: at ``sigma_t == 0`` no step noise is drawn -- the reference draws one and multiplies it by zero; the
+    values are the same, the consumption of the random stream is not."""
+
+    def __init__(self, diffusion, model, schedule="linear", alpha_generator_func=None, set_alpha_scale=None):
+        super().__init__(diffusion, model, schedule, alpha_generator_func, set_alpha_scale)
+        self.noise_fn = lambda shape: torch.randn(tuple(shape), device=self.engine.device, dtype=torch.float32)
+
+    # ---- schedule (ddim.py:25-54; util.py:55-83) ------------------------------------------------------------
+    def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.):
+        super().make_schedule(ddim_num_steps, ddim_discretize, 0.)             # timesteps, a_t, a_prev, sqrt(1 - a_t): float32
+        # util.py:78 as the reference's operand types evaluate it: ``alphas`` is a float32 torch tensor and ``alphas_prev`` a
+        # float64 numpy array, so ``(1 - alphas_prev) / (1 - alphas)`` runs as Tensor.__rtruediv__ = reciprocal(1 - alphas) in
+        # float32, times the float64 numerator; every other operation is float64.  A step rounds its sigma to float32.
+        a32, a, ap = self.ddim_alphas, self.ddim_alphas.astype(np.float64), self.ddim_alphas_prev.astype(np.float64)
+        recip = (np.float32(1.0) / (np.float32(1.0) - a32)).astype(np.float64)
+        self.ddim_sigmas = ddim_eta * np.sqrt(recip * (1 - ap) * (1 - a / ap))
+
+    @torch.no_grad()
+    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, eta=0.):
+        """``eta`` is an extension: the reference's ``sample`` always schedules eta 0 (ddim.py:59); its eta is reachable through
+        ``make_schedule(S, ddim_eta=eta)`` + ``ddim_sampling``, which works here too."""
+        self.make_schedule(ddim_num_steps=S, ddim_eta=eta)
+        return self.ddim_sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
+
+    @torch.no_grad()
+    def ddim_sampling(self, shape, input, uc, guidance_scale=1, mask=None, x0=None):
+        eng = self.engine
+        ops = eng.ops
+        dev = eng.device
+        b = shape[0]
+        img = input["x"]
+        if img is None:
+            img = torch.randn(shape, device=dev)
+            input["x"] = img
+        img = img.to(dev, torch.float32).contiguous()
+        guided = uc is not None and guidance_scale != 1
+        cond = self._cond(input)
+        if guided:
+            bank = type(cond).cat([cond, self._uncond(uc)])
+            pair = eng.gather_cond(bank, torch.arange(2 * b, device=dev))
+        else:
+            pair = cond
+        if mask is not None:
+            assert x0 is not None
+            x0 = x0.to(dev, torch.float32).expand(img.shape).contiguous()
+            mask = mask.to(dev, torch.float32)
+            mask = mask.expand(b, mask.shape[1] if mask.shape[1] == img.shape[1] else 1, *img.shape[2:]).contiguous()
+            sqrt_ac = self.diffusion.sqrt_alphas_cumprod.detach().to(torch.float32).cpu()
+            sqrt_1m_ac = self.diffusion.sqrt_one_minus_alphas_cumprod.detach().to(torch.float32).cpu()
+        time_range = np.flip(self.ddim_timesteps)
+        total = self.ddim_timesteps.shape[0]
+        alphas = self.alpha_generator_func(len(time_range)) if self.alpha_generator_func is not None else None
+        self._check_first_conv(alphas)
+        for i, step in enumerate(time_range):
+            self._apply_alpha(alphas, i)                                      # ddim.py:85-88
+            index = total - i - 1
+            input["timesteps"] = torch.full((b,), int(step), device=dev, dtype=torch.long)
+            if mask is not None:                                              # ddim.py:94-98
+                img = ops.q_sample_blend(x0, self.noise_fn(img.shape), mask, img, float(sqrt_ac[int(step)]),
+                                         float(sqrt_1m_ac[int(step)]), ops.empty(img.shape, torch.float32))
+                input["x"] = img
+            # p_sample_ddim (ddim.py:107-131): one batched [cond | uncond] forward, its raw halves into the fused update
+            t = torch.full((b,), float(step), device=dev, dtype=torch.float32)
+            if guided:
+                e2 = eng.forward_cond(img, t, pair, out=eng.buf("smp.eps2", (2 * b,) + tuple(img.shape[1:]), torch.float32), paired=True)
+                e_c, e_u = e2[:b], e2[b:]
+            else:
+                e_c, e_u = eng.forward_cond(img, t, pair), None
+            sigma = float(np.float32(self.ddim_sigmas[index]))
+            noise = self.noise_fn(img.shape) if sigma != 0 else None
+            img = ops.ddim_update(img, e_c, e_u, guidance_scale, float(self.ddim_alphas[index]), float(self.ddim_alphas_prev[index]),
+                                  sigma, float(self.ddim_sqrt_one_minus_alphas[index]), noise, ops.empty(img.shape, torch.float32))
+            input["x"] = img
+        return img

@@ -491,6 +491,30 @@ class HipOps:
                    "idf_plms_update")
         return out
 
+    def ddim_update(self, x, e_cond, e_uncond, guidance, a_t, a_prev, sigma_t, sqrt_1m_at, noise, out, pred_x0=None):
+        """One DDIM step behind the forward (ddim.py:110-131): guidance (``e_uncond`` None: unguided), pred_x0, dir_xt and the
+        noise term (``noise`` None: none, needs sigma_t == 0).  fp32, contiguous, all of ``out``'s size; ``out`` may be ``x``."""
+        for t in (x, e_cond, out) + tuple(t for t in (e_uncond, noise, pred_x0) if t is not None):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == out.numel()
+        _lib.check(self.lib.idf_ddim_update(_p(x), _p(e_cond), _p(e_uncond), float(guidance), float(a_t), float(a_prev),
+                                            float(sigma_t), float(sqrt_1m_at), _p(noise), _p(out), _p(pred_x0), out.numel(),
+                                            self._stream()), "idf_ddim_update")
+        return out
+
+    def q_sample_blend(self, x0, noise, mask, img, sqrt_ac, sqrt_1m_ac, out):
+        """q_sample + the inpainting blend (ldm.py:17-20, ddim.py:94-98): out = (sqrt_ac x0 + sqrt_1m_ac noise) mask + (1 - mask) img.
+        x0 / noise / img / out [B,C,H,W] fp32, mask [B,1,H,W] or [B,C,H,W]; ``out`` may be ``img``."""
+        B, Cc = out.shape[0], out.shape[1]
+        HW = out.numel() // (B * Cc)
+        assert mask.dim() == out.dim() and mask.shape[0] == B and mask.shape[1] in (1, Cc) and mask.shape[2:] == out.shape[2:]
+        for t in (x0, noise, img):
+            assert t.shape == out.shape
+        for t in (x0, noise, mask, img, out):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        _lib.check(self.lib.idf_q_sample_blend(_p(x0), _p(noise), _p(mask), _p(img), float(sqrt_ac), float(sqrt_1m_ac), _p(out),
+                                               B, Cc, HW, int(mask.shape[1]), self._stream()), "idf_q_sample_blend")
+        return out
+
     def mis_merge(self, lat, boxes_i32, out, mode):
         n1, B, Cc, H, W_ = lat.shape
         assert lat.is_contiguous() and out.is_contiguous()
