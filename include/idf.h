@@ -101,10 +101,13 @@ const char* idf_build_info(void);
  *   IDF_TUNE_QKV_ROW (round 6): the fused q | k | v projection of the C = 320 level (K = 320, N = 960, vt_col0 = 640, M % 256 == 0) and
  *     of the C = 640 level (K = 640, N = 1920, vt_col0 = 1280, M % 128 == 0), statistics handed in, from two tiles per CU, on
  *     qkv320w_kernel / qkv640w_kernel (activation rows resident in registers): 0 = never, 1 = when the shape qualifies (default).
- *     Env IDF_QKV_ROW.
+ *     Env IDF_QKV_ROW.  Same per-element error against fp64 as the persistent kernel; the two round 0.1 % of the outputs apart (one
+ *     16-bit ulp) at |mean| / std < 1 of the rows, a share that grows in proportion to that ratio (up to 9 % at 100): the mean term
+ *     is folded as a k-step of 16-bit hi + lo products, not as an fp32 fma behind the sum (csrc/qkv_fused.hip).
  *   IDF_TUNE_GEGLU_ROW (round 6): the GEGLU projection of the C = 640 level (K = 640, N = 5120, epilogue BIAS | GEGLU | GEGLU_P32 |
  *     LN_ROW with the statistics handed in, M % 128 == 0, from two tiles per CU) on geglu640w_kernel: 0 = never, 1 = when the shape
- *     qualifies (default).  Env IDF_GEGLU_ROW.
+ *     qualifies (default).  Env IDF_GEGLU_ROW.  Same per-element error against fp64 as the persistent kernel; the two round up to
+ *     0.2 % of the outputs apart at |mean| / std < 1 of the rows, up to 12 % (fp16; 1.5 % bf16) at a ratio of 100, one ulp at most.
  *   IDF_TUNE_PROJ_ROW (knob 9; new enum values within ABI 5; id 8 stays unassigned -- it is the id the C-ABI test probes as
  *     the unknown knob, idf_set_tuning(8, ..) == IDF_E_ARG): the N = K = 320 projections of the C = 320 level (batch 1, no vt_out,
  *     M % 32 == 0, M >= 512 x the CU count -- two 256-row tiles per CU, the rule of IDF_TUNE_QKV_ROW; epilogue BIAS, BIAS | RES, BIAS | RES | GATE, or BIAS | LN_ROW with the statistics

@@ -28,7 +28,12 @@
 // statistics handed in (ln_stats != NULL) and BIAS; everything else stays on gemm_big.hip.  Same arithmetic per output element
 // (fp32 accumulation over k = 0 .. 319 in the same order), except that the mean term -mu c[n] rides the MFMAs as a 21st k-step of
 // four 16-bit products (c and -mu split hi + lo, 2^-17 each) instead of an fp32 fma per element: measured error against fp64
-// identical to the persistent kernel's (1.66e-3 bf16 / 2.07e-4 fp16 rel-RMS), 0.1 % of the outputs differ by one 16-bit ulp.
+// identical to the persistent kernel's (1.66e-3 bf16 / 2.07e-4 fp16 rel-RMS), 0.1 % of the outputs differ by one 16-bit ulp -- at
+// the |mean| / std below 1 of this model's LayerNorm inputs.  The share grows in proportion to |mean| / std, because the term is
+// |mean| / std times the output and is folded at another place of the fp32 chain: measured 1.9 % (bf16) / 0.3 % (fp16) of the outputs
+// at a ratio of 10, 8.7 % / 2.0 % at 100 (qkv640w_kernel: 0.1 % / 1.1 % and 0.8 % / 7.0 %), never more than one ulp, and both kernels
+// stay inside the same per-element bound against fp64, U |want| + K 2^-24 |A| |W|^T rstd + 2^-16 rstd |mu| |c|, at every ratio
+// (tests/test_row_kernels_gpu.py; tests/row_kernel_cases.py pair_fraction_bar derives the upper estimate the test asserts).
 // LDS: 2 x 40 KB ring + 15.5 KB (the c table as 16-bit hi | lo pairs) + 3.75 KB (d) + 1 KB (the waves' rstd tables) + 4 x 8 KB staging = 132 KB.
 #include "mw_row.h"
 
