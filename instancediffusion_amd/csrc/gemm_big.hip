@@ -25,10 +25,9 @@
 // tile needs 28.8 B/clk at 100 % MFMA (tools/ubench/dma_mix.hip; round 2's 5.6 / 34 were a ubench artefact) -- but power: the
 // kernel's mix of MFMAs, fragment reads and LDS-DMA sustains 1.11 PFLOP/s at 1.35-1.48 GHz even without any synchronisation
 // (tools/ubench/mfma_power.hip), pure MFMA 1.75-1.88 at 1.65-1.79 GHz (mfma_sustain.hip).
-// Round 3: (a) the geometries that were measured slower (two 4-wave workgroups per CU, the role-split ping-pong kernel, the
-// four-stage 32-deep ring, the end / spread fill schedules) left the library -- source snapshot
-// profiles/archive_rejected_kernels/gemm_big_r02.hip, numbers profiles/r02_pp_*, r02_shape_profile_B64_fill_*; (b) fused q | k | v
-// projection (VT): the output tiles whose columns lie at or beyond `vt_col0` run the SAME K loop with the MFMA operands
+// The geometries, fill schedules and the staged epilogue that were measured slower are not in this file: what they were and
+// what they measured is listed in profiles/archive_rejected_kernels/README.md.
+// Round 3: fused q | k | v projection (VT): the output tiles whose columns lie at or beyond `vt_col0` run the SAME K loop with the MFMA operands
 // swapped, so a lane ends up with 16 consecutive TOKENS of one channel and stores V transposed (V^T[channel][token], the
 // layout the P.V MFMA's A operand wants) -- one launch reads the activation tile once for q, k and V^T instead of a second
 // GEMM (M = C, whose 256-row tiles were 62 % padding at C = 320) re-reading it.
@@ -44,21 +43,16 @@ namespace {
 
 IDF_ZERO_PAGE(idf_zero_page);
 
-// Wave tile: IDF_WAVE_ROWS rows x BN/2 columns.  64 (library): eight waves per workgroup, two per SIMD, 160 accumulator
-// registers per lane.  128 (experiment of tools/ubench/big_trace.hip, see profiles/DESIGN_r01_r05_full.md "What bounds the GEMM family"): four waves,
-// one per SIMD with the whole 512-register budget -- 9 fragment reads per 20 MFMAs instead of 7 per 10.
-#ifndef IDF_WAVE_ROWS
-#define IDF_WAVE_ROWS 64
-#endif
-constexpr int WM = IDF_WAVE_ROWS, TM = WM / 32;
-constexpr int NWAVES = 2 * 256 / WM;          // waves per 256-row workgroup tile (8 or 4)
+// Wave tile: 64 rows x BN/2 columns (two 32-row fragments): eight waves per 256-row workgroup tile, two per SIMD, 160 accumulator
+// registers per lane at BN = 320.
+constexpr int WM = 64, TM = 2, NWAVES = 8;
 
 template <int I> struct IC { static constexpr int value = I; };
 template <int I, int N, int STEP, class F> __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (I < N) { f(IC<I>{}); static_for<I + STEP, N, STEP>(f); }
 }
 
-// ---------------- tile epilogue (shared by the lock-step and the ping-pong kernel): no LDS, no barrier.
+// ---------------- tile epilogue: no LDS staging of the output, no workgroup barrier.
 // acc[a][b][4q+e] = D[n = a*32 + 8q + 4hi + e][m = b*32 + l31].  Two v_permlane32_swap per register pair
 // (q0 <-> q2, q1 <-> q3 between the lane halves) leave every lane with 16 CONSECUTIVE columns of its row:
 // n = a*32 + 16*hi + [0,16)  ->  two 16-B stores per (a, b), 16-B residual / rowbias loads, float4 bias loads.
@@ -69,33 +63,6 @@ template <int I, int N, int STEP, class F> __device__ __forceinline__ void stati
 // finalize kernel replaces the pass that re-read the whole output (65 of them per forward in round 2).
 // GLU: the kernel instantiation that serves ONLY period-32 GEGLU launches on the 5-fragment (320-wide) wave tile: compiled with
 // nothing but that branch -- carrying it as a run-time branch in the other 320-wide kernels cost them ~290 spilled VGPRs.
-// ---- coalesced epilogue accesses (round 4).  After the v_permlane32_swap exchange a lane owns 16 consecutive columns of ITS
-// row, so a 16-B store / residual load instruction touches 32 different rows in 64 separate 16-B pieces: 64 requests per
-// instruction, and the CU's vector-memory path retires about one request per cycle -- 8 waves x 20 stores x 64 requests =
-// 10 k cycles per tile, which IS the 13-20 k-cycle epilogue of the cycle traces (52 k with the residual loads), whatever the
-// HBM does (de-phasing the workgroups changed nothing: profiles/r04_big_sched_walk_dephase_epivm.log).  Now a 32 x 32 fragment
-// (2 KB of 16-bit values) goes through a wave-private 2-KB LDS slot -- the 16 KB the two 72-KB ring stages leave of the CU's
-// 160 KB -- and is stored (the residual: loaded) with 4 adjacent lanes on the 64 contiguous bytes of one row: 16 requests per
-// instruction.  Same values, same arithmetic, same instruction count; wave-private, so still no workgroup barrier.
-// Slot image: [32 rows][64 B], 16-B piece ^= f(row) with f = ((b2 ^ b3) << 1) | (b1 ^ b3 ^ b4) of the row's bits: both access
-// patterns (lane = row with two pieces: "math layout"; 4 lanes per row: "store layout") are bank-conflict-free for
-// ds_read_b128's 16-lane groups and ds_write_b128's 8-lane groups.
-// DEFAULT OFF: measured -0.1 ... -8 % (profiles/r04_big_stage_epilogue.log) -- the ~12 B/clk per CU at which an epilogue
-// drains is not a request-count limit -- so build.sh does not define IDF_EPI_STAGE and the GPU suite does not cover the staged
-// path; it is kept as the A/B build `tools/ubench/big_sched_stage1` measured.  The wave-private 2-KB slots themselves are NOT
-// dead weight: the fused q | k | v projection parks its in-loop LayerNorm statistics there (LNS + VT) and, since round 5, the GST
-// conv epilogue passes its 2 x 160 column totals through them.
-#ifndef IDF_EPI_STAGE
-#define IDF_EPI_STAGE 0
-#endif
-__device__ __forceinline__ int stg_f(int row) {
-  return ((((row >> 2) ^ (row >> 3)) & 1) << 1) | (((row >> 1) ^ (row >> 3) ^ (row >> 4)) & 1);
-}
-// piece `pc` (0..3) of row `row` of the slot
-__device__ __forceinline__ u32x4* stg_at(char* stg, int row, int pc) {
-  return reinterpret_cast<u32x4*>(stg + row * 64 + ((pc ^ stg_f(row)) << 4));
-}
-
 // GST (round 5): GroupNorm statistics of the tile's OUTPUT as a by-product ("statistics out of the producer's
 // epilogue") -- per wave, for its 64 rows x BN/2 columns, one (mean, M2) pair per 32-group GroupNorm group into
 // p.gn_partial[sample][64-row chunk][group][2]: exactly the partial-summary layout gn_apply merges (norms.hip), so the
@@ -135,24 +102,12 @@ __device__ __forceinline__ void big_epilogue(const CoreParams& p, f32x16 (&acc)[
                                              int wn, int l31_in, int hi_in, float gate, char* stg_in, const float* lnm = nullptr,
                                              const float* lnr = nullptr) {
   constexpr int WN = BN / 2;
-  constexpr bool STG = IDF_EPI_STAGE != 0;
   const int epi = p.epi;
   // opaque copies: everything the epilogue derives from the lane id (row / column offsets, slot addresses) is then computed
   // HERE, per tile, instead of being hoisted out of the tile loop and kept alive -- or spilled -- across the K loop
   int l31 = l31_in, hi = hi_in;
   asm volatile("" : "+v"(l31), "+v"(hi));
   char* const stg = stg_in;
-  const int sl_row = (l31 + 32 * hi) >> 2, sl_pc = l31 & 3;       // store layout: lane -> row sl_row (+ 16), piece sl_pc
-  // 32 rows x 64 B from the slot to rows m_base.. of a 16-bit matrix (column c0), 16 rows x 64 contiguous bytes per instruction
-  auto stg_store64 = [&](unsigned short* base, int ld, int m_base, int c0) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int row = sl_row + 16 * i;
-      const u32x4 t = *stg_at(stg, row, sl_pc);
-      if (m_base + row < p.M) *reinterpret_cast<u32x4*>(base + (size_t)(m_base + row) * ld + c0 + sl_pc * 8) = t;
-    }
-  };
   const int m_tile = seq / tiles_n;
   const int n0 = (seq - m_tile * tiles_n) * BN, m0 = m_tile * BM;
   const int mw = m0 + wm * WM, nw = n0 + wn * WN;
@@ -233,19 +188,7 @@ __device__ __forceinline__ void big_epilogue(const CoreParams& p, f32x16 (&acc)[
         }
         const int m = mw + b * 32 + l31;
         unsigned short* const obase = reinterpret_cast<unsigned short*>(p.out);
-        if constexpr (STG) {
-          // a fragment leaves 32 B per row (the lane's 8 columns + its partner half's): two fragments fill the slot's 64-B rows
-          *stg_at(stg, l31, 2 * (a & 1) + hi) = pack8<DT>(v);
-          if constexpr ((a & 1) == 1) {
-            stg_store64(obase, p.ldo, mw + b * 32, (nw >> 1) + (a - 1) * 16);
-          } else if constexpr (a == TN - 1) {                 // odd fragment count: the last one goes out alone, 32 B per row
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            const int lane = l31 + 32 * hi, row = lane >> 1, pc = lane & 1;
-            const u32x4 t = *stg_at(stg, row, pc);
-            if (mw + b * 32 + row < p.M)
-              *reinterpret_cast<u32x4*>(obase + (size_t)(mw + b * 32 + row) * p.ldo + (nw >> 1) + a * 16 + pc * 8) = t;
-          }
-        } else if (m < p.M) {
+        if (m < p.M) {
           unsigned short* op = obase + (size_t)m * p.ldo + (npk >> 1) + 8 * hi;
           *reinterpret_cast<u32x4*>(op) = pack8<DT>(v);
         }
@@ -294,11 +237,7 @@ __device__ __forceinline__ void big_epilogue(const CoreParams& p, f32x16 (&acc)[
           float v[16];
           swap16(o, v);
           const int m = mw + b * 32 + l31;
-          if constexpr (STG) {
-            *stg_at(stg, l31, 2 * hi) = pack8<DT>(v);
-            *stg_at(stg, l31, 2 * hi + 1) = pack8<DT>(v + 8);
-            stg_store64(reinterpret_cast<unsigned short*>(p.out), p.ldo, mw + b * 32, npk >> 1);
-          } else if (m < p.M) {
+          if (m < p.M) {
             unsigned short* op = reinterpret_cast<unsigned short*>(p.out) + (size_t)m * p.ldo + (npk >> 1) + 16 * hi;
             *reinterpret_cast<u32x4*>(op) = pack8<DT>(v);
             *reinterpret_cast<u32x4*>(op + 8) = pack8<DT>(v + 8);
@@ -379,23 +318,9 @@ __device__ __forceinline__ void big_epilogue(const CoreParams& p, f32x16 (&acc)[
         if (epi & IDF_EPI_RES) {
           const float gm = (epi & IDF_EPI_GATE) ? gate : 1.0f;
           float r[16];
-          if constexpr (STG) {
-            // the fragment's 32 x 64 B of the residual: 16 rows x 64 contiguous bytes per load instruction, then each lane
-            // picks its own row's 32 B out of the slot
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-              const int row = sl_row + 16 * i;
-              const int mr = min(mw + b * 32 + row, p.M - 1);
-              *stg_at(stg, row, sl_pc) = *reinterpret_cast<const u32x4*>(p.res + (size_t)mr * p.ldr + nw + a * 32 + sl_pc * 8);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            unpack8<DT>(*stg_at(stg, l31, 2 * hi), r);
-            unpack8<DT>(*stg_at(stg, l31, 2 * hi + 1), r + 8);
-          } else {
-            const unsigned short* rr = p.res + (size_t)mc * p.ldr + n;
-            unpack8<DT>(*reinterpret_cast<const u32x4*>(rr), r);
-            unpack8<DT>(*reinterpret_cast<const u32x4*>(rr + 8), r + 8);
-          }
+          const unsigned short* rr = p.res + (size_t)mc * p.ldr + n;
+          unpack8<DT>(*reinterpret_cast<const u32x4*>(rr), r);
+          unpack8<DT>(*reinterpret_cast<const u32x4*>(rr + 8), r + 8);
 #pragma unroll
           for (int j = 0; j < 16; ++j) v[j] = fmaf(gm, v[j], r[j]);
         }
@@ -407,12 +332,7 @@ __device__ __forceinline__ void big_epilogue(const CoreParams& p, f32x16 (&acc)[
           }
         } else {
           const u32x4 q0 = pack8<DT>(v), q1 = pack8<DT>(v + 8);
-          if constexpr (STG) {
-            asm volatile("" ::: "memory");            // the residual reads of the slot above are done before it is rewritten
-            *stg_at(stg, l31, 2 * hi) = q0;
-            *stg_at(stg, l31, 2 * hi + 1) = q1;
-            stg_store64(reinterpret_cast<unsigned short*>(p.out), p.ldo, mw + b * 32, nw + a * 32);
-          } else if (m < p.M) {
+          if (m < p.M) {
             unsigned short* o = reinterpret_cast<unsigned short*>(p.out) + (size_t)m * p.ldo + n;
             *reinterpret_cast<u32x4*>(o) = q0;
             *reinterpret_cast<u32x4*>(o + 8) = q1;
@@ -797,22 +717,9 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
   constexpr int NPOS = (BKT / 16) * TN;                   // (k-step, weight fragment) positions of a K-tile: TM MFMAs each
   // Fill schedule (see the K loop).  OLD_LATE: which half of the workgroup enqueues the next K-tile from inside its MFMAs --
   // the OLDER waves 0..3 (320-wide tiles, at 7/8 of their MFMAs) or the younger waves 4..7 (at 1/2: the round-2 schedule,
-  // kept for the 256- and 128-wide tiles, where the new one measured no better).  -DIDF_LATE_OLD / _NUM / _DEN: the
-  // experiment knobs of tools/ubench/big_trace.hip.
-#ifdef IDF_LATE_NUM
-  constexpr bool OLD_LATE = IDF_LATE_OLD != 0;
-  constexpr int LATE_POS = NPOS * IDF_LATE_NUM / IDF_LATE_DEN;
-#else
+  // kept for the 256- and 128-wide tiles, where the new one measured no better).
   constexpr bool OLD_LATE = BN == 320;
   constexpr int LATE_POS = OLD_LATE ? NPOS * 7 / 8 : NPOS / 2;
-#endif
-  // one wave per SIMD (NW == 4): there is no partner to hide a burst under, every wave enqueues one piece per position
-  constexpr bool SPREAD = NW == 4;
-#ifdef IDF_SPREAD_PPP
-  constexpr int PPP = IDF_SPREAD_PPP;                      // pieces per position of the spread fill (from position 0 on)
-#else
-  constexpr int PPP = (DPW + NPOS - 1) / NPOS;
-#endif
   // `late_fill`: this wave enqueues the next K-tile's LDS-DMA pieces from the MIDDLE of its MFMAs (see the K loop).
   // SWAPT: MFMA operands swapped (transposed-V tiles of the fused q | k | v projection): acc[a][b] then holds
   // D[m = b*32 + 8q + 4hi + e][n = a*32 + l31] -- a lane owns a channel, its registers run over tokens.
@@ -843,20 +750,10 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
       static_for<0, TN, 1>([&](auto AI) {
         constexpr int a = decltype(AI)::value;
         constexpr int pos = ks * TN + a;
-        if constexpr (NW == 4) {
-          // accumulator fragments 0..15 (256 registers) pinned to the AGPR file, 16..19 to the VGPR file
-          static_for<0, TM, 1>([&](auto BI) {
-            constexpr int b = decltype(BI)::value;
-            constexpr bool AG = a * TM + b < 16;
-            if constexpr (SWAP) Elem<DT>::template mfma32_pin<AG>(af[cur][b], wf[cur][a], acc[a][b]);
-            else Elem<DT>::template mfma32_pin<AG>(wf[cur][a], af[cur][b], acc[a][b]);
-          });
-        } else {
 #pragma unroll
-          for (int b = 0; b < TM; ++b) {
-            if constexpr (SWAP) acc[a][b] = Elem<DT>::mfma32(af[cur][b], wf[cur][a], acc[a][b]);
-            else acc[a][b] = Elem<DT>::mfma32(wf[cur][a], af[cur][b], acc[a][b]);
-          }
+        for (int b = 0; b < TM; ++b) {
+          if constexpr (SWAP) acc[a][b] = Elem<DT>::mfma32(af[cur][b], wf[cur][a], acc[a][b]);
+          else acc[a][b] = Elem<DT>::mfma32(wf[cur][a], af[cur][b], acc[a][b]);
         }
         if constexpr (LNS && a == 0) {                      // row sums of the A fragments this k-step multiplies: 16 VALU ops
 #pragma unroll
@@ -867,11 +764,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
               Elem<DT>::dot2c(lsq[b], af[cur][b][w], af[cur][b][w]);
             }
         }
-        if constexpr (SPREAD) {
-          if constexpr (pos * PPP < DPW) {
-            if (late_fill) static_for<pos * PPP, ((pos + 1) * PPP < DPW ? (pos + 1) * PPP : DPW), 1>([&](auto II) { issue_piece(st_fill, II); });
-          }
-        } else if constexpr (pos == LATE_POS - 1) {
+        if constexpr (pos == LATE_POS - 1) {
           if (late_fill) static_for<0, DPW, 1>([&](auto II) { issue_piece(st_fill, II); });
         }
       });
@@ -881,13 +774,11 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
 
   int seq = seq0;
   if (seq >= seq_end) return;
-  // De-phasing (round 4): a persistent launch whose tiles all cost the same runs its 256 workgroups in lock step, so every
-  // CU reaches its epilogue at the same moment: the store burst of a round (160 KB per CU, 41 MB per round) then meets an
-  // HBM that idled through the K loops, and the waves sit in store-issue back-pressure (cycle trace of `M262144 N2560 K320`:
-  // 19-20 k cycles of epilogue per tile for 20 stores per wave, ~4 TB/s of writes in bursts, 1.9 TB/s on average).  With
-  // p.dephase = P > 1 the workgroups of every XCD start in P groups, group g delayed by g / P of one tile's estimated
-  // duration, so at any moment only ~1 / P of the CUs are in their store burst.  The delay costs (P - 1) / P of a tile at
-  // the start of the launch; the dispatcher asks for it on launches of >= 8 rounds only.
+  // De-phased start (round 4; p.dephase = P > 1: the workgroups of every XCD start in P groups, group g delayed by g / P of one
+  // tile's estimated duration, so that the store bursts of a round do not coincide).  Measured +0 ... +4 % on two launches and
+  // -4 ... -20 % on the long-K ones (profiles/r04_big_sched_walk_dephase_epivm.log): the launcher always passes 0 and nothing
+  // sets it.  The block is still here because the compiler's output depends on it: without it the epilogue's loads, stores and
+  // waits come out in another order in 18 of the 40 instantiations (profiles/big_plain_code.md).
   if (p.dephase > 1) {
     const int ph = (int)(blockIdx.x >> 3) % p.dephase;
     const int units = ph * p.dephase_units / p.dephase;       // units of 1024 cycles
@@ -904,7 +795,8 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
   TR_DECL
   const int epi = p.epi;
   const float gate = (epi & IDF_EPI_GATE) ? p.gate[0] : 0.0f;
-  // wave-private 2-KB slot behind the ring: epilogue staging (big_epilogue) / the LNS statistics of a transposed tile
+  // wave-private 2-KB slot behind the ring: where a transposed tile (LNS + VT) parks its in-loop LayerNorm statistics and the
+  // GST epilogue passes its 2 x 160 column totals; no output goes through LDS
   char* const stg = reinterpret_cast<char*>(smem + NSTG * STAGE) + wave * 2048;
 
   // One output tile: accumulators cleared, the K loop, the epilogue.  SWAPT = the transposed-V tiles of the fused q | k | v
@@ -968,7 +860,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
       const bool fill = l_seq < seq_end;
       int st_fill = st_it + NSTG - 1;
       if (st_fill >= NSTG) st_fill -= NSTG;
-      const bool late = fill && (SPREAD || (OLD_LATE ? wave < NW / 2 : wave >= NW / 2));
+      const bool late = fill && (OLD_LATE ? wave < NW / 2 : wave >= NW / 2);
       if (fill && !late) {
         issue_dma(st_fill);
         ++issued;
@@ -980,7 +872,6 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
       if (++st_it == NSTG) st_it = 0;
     }
 
-    if constexpr (NW == 4) asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");   // inline-asm MFMAs: the compiler does not see their result latency
     // epilogue of tile seq: no workgroup barrier -- a wave that finishes its MFMAs early runs its epilogue while the other
     // wave of its SIMD is still in the K-loop
     float lnm[TM], lnr[TM];
@@ -1051,43 +942,22 @@ int num_cu() {
   return g_num_cu;
 }
 
-// Schedule settings of the persistent kernel (process-global, read once from the environment; idf_set_tuning may override).
-struct BigSched { int walk, dephase, dephase_min_rounds, dephase_epi_cycles, epi_vmcnt; };
-BigSched& big_sched() {
-  static BigSched sc = [] {
-    auto env = [](const char* name, int dflt, int lo, int hi) {
-      const char* e = getenv(name);
-      if (!e) return dflt;
-      const int v = atoi(e);
-      return (v < lo || v > hi) ? dflt : v;
-    };
-    BigSched c;
-    // measured defaults (profiles/r04_big_sched_walk_dephase_epivm.log, all bit-identical): the chunked walk pays only when
-    // an m-tile has >= 32 n-tiles (N = 10240: +6.7 %; -4 ... -18 % on the narrower launches) -> walk = 2 (automatic);
-    // the counted wait behind the epilogue is +0.3 ... +1.6 % on the K <= 640 launches and +-0 elsewhere -> on;
-    // the de-phased start is +0 ... +4 % on two launches and -4 ... -20 % on the long-K ones -> off.
-    c.walk = env("IDF_BIG_WALK", 2, 0, 2);
-    c.dephase = env("IDF_BIG_DEPHASE", 0, 0, 16);
-    c.dephase_min_rounds = env("IDF_BIG_DEPHASE_MIN_ROUNDS", 8, 1, 1 << 20);
-    c.dephase_epi_cycles = env("IDF_BIG_DEPHASE_EPI", 6000, 0, 1 << 20);
-    c.epi_vmcnt = env("IDF_BIG_EPIVM", 1, 0, 1);
-    return c;
-  }();
-  return sc;
-}
+// Which instantiation of gemm_kernel_big a launch runs: the kernel's bool template arguments as named bits.
+enum : unsigned { KB_CONV = 1, KB_SPLIT = 2, KB_LNS = 4, KB_VT = 8, KB_STATS = 16, KB_GLU = 32, KB_GST = 64, KB_FOLD = 128 };
 
-template <int DT, int BN, int NSTG, bool CONV, bool SPLIT = false, bool LNS = false, bool VT = false, bool STATS = false, bool GLU = false,
-          bool GST = false, bool FOLD = false>
+template <int DT, int BN, int NSTG, unsigned FLAGS = 0>
 int launch_big_cfg(const CoreParams& p, hipStream_t s, int splitk = 1) {
   constexpr int BM = 256, BKT = 64;
-  if constexpr (!SPLIT && !LNS && !VT && !STATS && !GLU && !GST && !FOLD && NSTG == 2) {
-    if (splitk > 1) return launch_big_cfg<DT, BN, NSTG, CONV, true>(p, s, splitk);
+  constexpr bool CONV = FLAGS & KB_CONV, SPLIT = FLAGS & KB_SPLIT, LNS = FLAGS & KB_LNS, VT = FLAGS & KB_VT, STATS = FLAGS & KB_STATS,
+                 GLU = FLAGS & KB_GLU, GST = FLAGS & KB_GST, FOLD = FLAGS & KB_FOLD;
+  if constexpr (!(FLAGS & ~KB_CONV) && NSTG == 2) {         // plain GEMM / conv asked to split: its SPLIT twin
+    if (splitk > 1) return launch_big_cfg<DT, BN, NSTG, (FLAGS & KB_CONV) | KB_SPLIT>(p, s, splitk);
   }
-  if constexpr (!SPLIT && !LNS && !CONV && !STATS && !GST && NSTG == 2) {
-    if ((p.epi & IDF_EPI_LN_ROW) && !p.ln_stats) return launch_big_cfg<DT, BN, NSTG, CONV, false, true, VT, false, GLU>(p, s, 1);
+  if constexpr (!(FLAGS & (KB_SPLIT | KB_LNS | KB_CONV | KB_STATS | KB_GST)) && NSTG == 2) {   // self-normalising LN_ROW: the LNS twin
+    if ((p.epi & IDF_EPI_LN_ROW) && !p.ln_stats) return launch_big_cfg<DT, BN, NSTG, (FLAGS & (KB_VT | KB_GLU)) | KB_LNS>(p, s, 1);
   }
   void (*kern)(const CoreParams, const int) = gemm_kernel_big<DT, BM, BN, BKT, NSTG, CONV, SPLIT, LNS, VT, STATS, GLU, GST, FOLD>;
-  constexpr int smem = NSTG * (BM + BN) * BKT * 2 + NWAVES * 2048;      // ring + one 2-KB slot per wave (160 KB at BN = 320)
+  constexpr int smem = NSTG * (BM + BN) * BKT * 2 + NWAVES * 2048;      // ring + one 2-KB slot per wave (see `stg` in the kernel): 160 KB at BN = 320
   static std::atomic<unsigned long long> attr_done{0};
   if (const int e = idf_lds_optin(reinterpret_cast<const void*>(kern), smem, attr_done)) return e;
   CoreParams q = p;
@@ -1099,17 +969,15 @@ int launch_big_cfg(const CoreParams& p, hipStream_t s, int splitk = 1) {
   if constexpr (FOLD) { q.fold_tiles = tiles_all; tiles = 4 * tiles_all; }   // four parity phases, phase-major
   const int slots = num_cu();
   const int grid = tiles < slots ? tiles : slots;
-  {                                                       // schedule knobs (all bit-identical; see the kernel)
-    const BigSched& sc = big_sched();
-    const int rounds = (tiles + slots - 1) / slots;
-    q.tile_walk = (!SPLIT && (sc.walk == 1 || (sc.walk == 2 && p.N / BN >= 32))) ? 1 : 0;
-    q.epi_vmcnt = sc.epi_vmcnt;
-    q.dephase = 0; q.dephase_units = 0;
-    if (!SPLIT && sc.dephase > 1 && rounds >= sc.dephase_min_rounds) {
-      q.dephase = sc.dephase;
-      q.dephase_units = (q.kt_full * 3400 + sc.dephase_epi_cycles) / 1024;
-    }
-  }
+  // the chunked walk pays only when an m-tile has >= 32 n-tiles (N = 10240: +6.7 %; -4 ... -18 % on the narrower launches;
+  // profiles/r04_big_sched_walk_dephase_epivm.log); either walk computes the same bits
+  q.tile_walk = !SPLIT && p.N / BN >= 32;
+  // The counted wait behind an epilogue (+0.3 ... +1.6 % on the K <= 640 launches, +-0 elsewhere; same log) is always on and the
+  // de-phased start always off.  Both stay kernel arguments: as compile-time constants they change the tile loop the compiler
+  // emits (epi_vmcnt = 1 restructures the young_stores wait ladder: +64 s_waitcnt, -119 s_nop in <*, 256, 320, 64, 2> and 6 of
+  // 40 descriptors move; profiles/big_plain_code.md).
+  q.epi_vmcnt = 1;
+  q.dephase = 0; q.dephase_units = 0;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NWAVES), smem, s, q, tiles);
   return idf_launch_status();
 }
@@ -1239,17 +1107,16 @@ int idf_launch_big(const CoreParams& p, int dtype, bool conv, bool force, hipStr
   pq.full_items = (int)full_items; pq.tail_m0 = tail_m0; pq.tail_rows = p.M - tail_m0;
   const bool glu320 = geglu && (p.epi & IDF_EPI_GEGLU_P32) && bn == 320;
 #define IDF_BIG_DISPATCH(DT)                                                                                              \
-  if (glu320) return launch_big_cfg<DT, 320, 2, false, false, false, false, false, true>(p, s);                           \
-  if (stats) return bn == 320 ? launch_big_cfg<DT, 320, 2, false, false, false, false, true>(ps, s)                        \
-                              : launch_big_cfg<DT, 256, 2, false, false, false, false, true>(ps, s);                       \
-  if (vt) return launch_big_cfg<DT, 320, 2, false, false, false, true>(p, s);                                             \
+  if (glu320) return launch_big_cfg<DT, 320, 2, KB_GLU>(p, s);                                                            \
+  if (stats) return bn == 320 ? launch_big_cfg<DT, 320, 2, KB_STATS>(ps, s) : launch_big_cfg<DT, 256, 2, KB_STATS>(ps, s); \
+  if (vt) return launch_big_cfg<DT, 320, 2, KB_VT>(p, s);                                                                 \
   if (bn == 128) {                       /* 128-wide tiles (the VAE's 128-channel convs at 512^2): 3 stages of 48 KB */  \
-    if (conv) return launch_big_cfg<DT, 128, 3, true>(p, s);                                                              \
-    return launch_big_cfg<DT, 128, 3, false>(p, s);                                                                       \
+    if (conv) return launch_big_cfg<DT, 128, 3, KB_CONV>(p, s);                                                           \
+    return launch_big_cfg<DT, 128, 3>(p, s);                                                                              \
   }                                                                                                                       \
-  if (gst) return launch_big_cfg<DT, 320, 2, true, false, false, false, false, false, true>(p, s);                         \
-  if (conv) return bn == 320 ? launch_big_cfg<DT, 320, 2, true>(pq, s, splitk) : launch_big_cfg<DT, 256, 2, true>(pq, s, splitk);   \
-  return bn == 320 ? launch_big_cfg<DT, 320, 2, false>(pq, s, splitk) : launch_big_cfg<DT, 256, 2, false>(pq, s, splitk);
+  if (gst) return launch_big_cfg<DT, 320, 2, KB_CONV | KB_GST>(p, s);                                                     \
+  if (conv) return bn == 320 ? launch_big_cfg<DT, 320, 2, KB_CONV>(pq, s, splitk) : launch_big_cfg<DT, 256, 2, KB_CONV>(pq, s, splitk);   \
+  return bn == 320 ? launch_big_cfg<DT, 320, 2>(pq, s, splitk) : launch_big_cfg<DT, 256, 2>(pq, s, splitk);
   if (dtype == IDF_BF16) { IDF_BIG_DISPATCH(IDF_BF16) }
   if (dtype == IDF_F16) { IDF_BIG_DISPATCH(IDF_F16) }
 #undef IDF_BIG_DISPATCH
@@ -1274,7 +1141,7 @@ int idf_launch_big_fold(const CoreParams& p, int dtype, bool force, hipStream_t 
   if ((unsigned long long)p.M * (unsigned long long)p.lda >= (1ull << 31) || 4ull * p.N * p.ldw >= (1ull << 31) ||
       items >= (1ll << 30) || (unsigned long long)p.M * 4ull >= (1ull << 31)) return IDF_BIG_UNSUPPORTED;
   ++idf_stat_big_launches;
-  if (dtype == IDF_BF16) return launch_big_cfg<IDF_BF16, 320, 2, true, false, false, false, false, false, false, true>(p, s);
-  if (dtype == IDF_F16) return launch_big_cfg<IDF_F16, 320, 2, true, false, false, false, false, false, false, true>(p, s);
+  if (dtype == IDF_BF16) return launch_big_cfg<IDF_BF16, 320, 2, KB_CONV | KB_FOLD>(p, s);
+  if (dtype == IDF_F16) return launch_big_cfg<IDF_F16, 320, 2, KB_CONV | KB_FOLD>(p, s);
   return IDF_E_UNSUPPORTED;
 }

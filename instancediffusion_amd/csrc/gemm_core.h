@@ -35,9 +35,10 @@ struct CoreParams {
   // GroupNorm partials of the output as a by-product of the persistent kernel's conv epilogue (round 5): (mean, M2) per
   // (sample, 64-row chunk, group) in gn_partial[sample][gn_hw / 64][32][2]; gn_hw = rows per sample
   float* gn_partial; int gn_hw;
-  // persistent-kernel schedule (round 4; every setting computes the same bits): tile_walk 0 = strided, 1 = chunked;
-  // dephase = P start groups per XCD (0 / 1: off), dephase_units = one tile's estimated duration in units of 1024 cycles;
-  // epi_vmcnt = 1: the first K-tile behind an epilogue waits with a counted vmcnt (the epilogue's stores drain under it)
+  // persistent-kernel schedule (round 4; every setting computes the same bits), set by launch_big_cfg alone: tile_walk 0 =
+  // strided, 1 = chunked; dephase = P start groups per XCD (always 0: off), dephase_units = one tile's estimated duration in
+  // units of 1024 cycles; epi_vmcnt (always 1): the first K-tile behind an epilogue waits with a counted vmcnt (the epilogue's
+  // stores drain under it).  The two constants are arguments because of what the compiler makes of the kernel without them
   int tile_walk; int dephase; int dephase_units; int epi_vmcnt;
   // conv gather: zero rows / columns in front of the image (the window origin is yo * stride - pad_lo).  1 = the symmetric
   // pad 1 of idf_conv3x3; 0 = idf_conv3x3_down (the VAE encoder's Downsample pads right and bottom only).  Wave-uniform.

@@ -7,7 +7,9 @@ The row-resident kernels (mlp320w / qkv320w / qkv640w / geglu640w) depend on mor
 counted vmcnt / lgkmcnt, so the ORDER of every memory, LDS, MFMA and wait instruction the compiler emits around the streams is
 part of their correctness.  `skeleton()` extracts that order; to show that an edit of those files left it alone:
     python tools/check_attn4w_isa.py --compare OLD_TREE NEW_TREE [FILE:KERNEL ...]
-(without FILE:KERNEL pairs, e.g. attention8.hip:attn8_kernel, the row-resident kernels are compared).  Instantiations are paired
+(without FILE:KERNEL pairs, e.g. attention8.hip:attn8_kernel, the row-resident kernels are compared).  With --from=MNEMONIC in
+front of the trees the ordered sequences are compared from the kernel's first MNEMONIC on (--from=s_barrier: an edit of the
+prologue's scalar code, e.g. a kernel argument that went; see compare()).  Instantiations are paired
 by demangled name; the OLD_TREE halves a kernel of DROPPED_ARG lost are reported as removed, any other instantiation that only one
 tree has fails the comparison."""
 import collections
@@ -27,11 +29,13 @@ ROW_KERNELS = [("mlp_fused.hip", "mlp320w_kernel"), ("mlp_fused.hip", "mlp320_ke
                ("qkv640_fused.hip", "qkv640w_kernel"), ("geglu_fused.hip", "geglu640w_kernel")]
 ORDERED = ("global_", "buffer_", "flat_", "scratch_", "ds_", "s_load", "s_barrier", "v_mfma", "v_accvgpr")
 # kernels that lost a trailing template argument: the OLD_TREE instantiations with this value of it pair with the new ones
-DROPPED_ARG = {"gemm_kernel": "true", "gemm_kernel_dma": "false"}
+DROPPED_ARG = {}
 # ... and the kernels bound by the descriptor and the COUNTED class counts only: every wait in them is the compiler's own (no
 # inline-asm LDS-DMA, no hand-counted vmcnt), so a differing order is printed but does not fail the comparison
 UNORDERED = ("gemm_kernel", "gemm_kernel_dma", "splitk_reduce_kernel")
 COUNTED = ("v_mfma", "ds_", "global_", "s_barrier", "s_waitcnt")
+# compare(start=...): the classes that may neither come nor go when the code in front of `start` (scalar loads, their waits) moves
+COUNTED_FROM = ("v_mfma", "ds_", "global_", "buffer_", "scratch_", "s_barrier")
 DESCRIPTOR = ("next_free_vgpr", "next_free_sgpr", "accum_offset", "private_segment_fixed_size", "group_segment_fixed_size")
 
 
@@ -78,11 +82,14 @@ def skeleton(src, kernel, extra=()):
     return out
 
 
-def compare(old_tree, new_tree, kernels=ROW_KERNELS):
+def compare(old_tree, new_tree, kernels=ROW_KERNELS, start=None):
     """0 when every kernel of `kernels` [(file, kernel)] in new_tree has the ordered sequence (UNORDERED kernels: the COUNTED class
     counts) and the descriptor of old_tree's, and no instantiation came or went but the halves a DROPPED_ARG kernel lost;
-    prints the instructions added / removed where the mnemonic multisets differ (address arithmetic may; nothing else should)"""
+    prints the instructions added / removed where the mnemonic multisets differ (address arithmetic may; nothing else should).
+    start: compare the ordered sequences from the first occurrence of this mnemonic on, and let s_waitcnt come and go (COUNTED_FROM)"""
     bad = False
+    counted = COUNTED_FROM if start else COUNTED
+    tail = lambda seq: seq[seq.index(start):] if start in seq else seq
     for f, kernel in kernels:
         a, b = (skeleton(os.path.join(t, "instancediffusion_amd", "csrc", f), kernel) for t in (old_tree, new_tree))
         if kernel in DROPPED_ARG:
@@ -95,10 +102,10 @@ def compare(old_tree, new_tree, kernels=ROW_KERNELS):
             print(f"{k}: NEW, no instantiation of {old_tree} to compare with")
         bad |= bool(set(b) - set(a)) or not b
         for k in sorted(set(a) & set(b)):
-            same_seq, same_desc = a[k]["seq"] == b[k]["seq"], a[k]["desc"] == b[k]["desc"]
+            same_seq, same_desc = tail(a[k]["seq"]) == tail(b[k]["seq"]), a[k]["desc"] == b[k]["desc"]
             add, rem = b[k]["mnemonics"] - a[k]["mnemonics"], a[k]["mnemonics"] - b[k]["mnemonics"]
-            same_cls = not any(m.startswith(COUNTED) for m in (*add, *rem))
-            print(f"{k}: {len(b[k]['seq'])} ordered entries {'same' if same_seq else 'DIFFER'}; descriptor {b[k]['desc']} "
+            same_cls = not any(m.startswith(counted) for m in (*add, *rem))
+            print(f"{k}: {len(tail(b[k]['seq']))} ordered entries {'same' if same_seq else 'DIFFER'}; descriptor {b[k]['desc']} "
                   f"{'same' if same_desc else 'DIFFERS from ' + str(a[k]['desc'])}; {sum(b[k]['mnemonics'].values())} instructions"
                   f" added {dict(add)} removed {dict(rem)}")
             bad |= not (same_desc and same_cls and (same_seq or kernel in UNORDERED))
@@ -128,8 +135,9 @@ def check(extra=(), src=SRC, kernel="attn4w_kernel"):
 
 if __name__ == "__main__":
     if sys.argv[1:2] == ["--compare"]:
+        start = sys.argv.pop(2)[len("--from="):] if sys.argv[2].startswith("--from=") else None
         pairs = [tuple(a.split(":", 1)) for a in sys.argv[4:]] or ROW_KERNELS
-        sys.exit(compare(os.path.abspath(sys.argv[2]), os.path.abspath(sys.argv[3]), pairs))
+        sys.exit(compare(os.path.abspath(sys.argv[2]), os.path.abspath(sys.argv[3]), pairs, start))
     rep = check(sys.argv[1:])
     bad = False
     for k, v in rep.items():

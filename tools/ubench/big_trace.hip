@@ -8,8 +8,7 @@
 // Build (from the repo root; ~1 min):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form -DIDF_BIG_TRACE -Iinclude -Iinstancediffusion_amd/csrc \
 //         tools/ubench/big_trace.hip -o tools/ubench/big_trace
-// Without -DIDF_BIG_TRACE the program only times the launches (and prints the output checksums): the A/B harness for K-loop
-// schedule variants (-DIDF_LATE_OLD=0|1 -DIDF_LATE_NUM=.. -DIDF_LATE_DEN=..: which waves enqueue late, and where), whose outputs must be bit-identical.
+// Without -DIDF_BIG_TRACE the program only times the launches and prints the output checksums.
 // Run: tools/ubench/big_trace [reps]     (about 10 s on the GPU; no Python)
 #include "../../instancediffusion_amd/csrc/gemm_big.hip"
 #include <cstdio>
