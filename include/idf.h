@@ -363,6 +363,20 @@ int idf_q_sample_blend(const float* x0, const float* noise, const float* mask, c
  * latent box (boxes: int32 [n_inst][4] = int(box*latent_size), reference index order dim2<-x, dim3<-y).      */
 int idf_mis_merge(const float* lat, const int* boxes, float* out, int n_inst, int B, int C, int H, int W,
                   int mode, void* stream);
+/* The same merge over a RAGGED unit list: a batch of images with different instance counts (PLMSSamplerInst.sample_layouts), one
+ * launch for the whole batch.  Added within ABI 5: a new symbol only.  lat: [U][C][H][W] fp32, the unit latents image after image;
+ * unit_off: DEVICE int32 [B+1], image b owns the units unit_off[b] .. unit_off[b+1]-1 and the first of them is its global
+ * (full-conditioning) trajectory; out: [B][C][H][W].
+ *   mode 0: s = 0.f; for k in image b's units, in order: s += lat[k]; out = s / (float)count   (idf_mis_merge's operation order,
+ *           each operation rounded on its own: equal counts give idf_mis_merge's result bit for bit)
+ *   mode 1: the global unit, then every later unit of the image overwrites its latent box (boxes: int32 [U][4], the entry of a
+ *           global unit is ignored; dim 2 sliced with box[0]:box[2], dim 3 with box[1]:box[3], later units win)
+ * No allocation, no synchronisation; hipGraph-capturable.  16-B accesses where lat and out are 16-B aligned and C*H*W % 4 == 0,
+ * scalar accesses otherwise (decided per launch).  The launcher cannot read the table: the kernel clamps every offset it loads
+ * to [0, U], so a wrong table cannot send a load outside lat; an image left without units is written as zeros.  IDF_E_ARG before
+ * any launch: a null lat / unit_off / out, B < 1, U < B, a non-positive dimension, mode not 0 or 1, mode 1 with boxes == NULL. */
+int idf_mis_merge_ragged(const float* lat, const int* unit_off, const int* boxes /* mode 1, else NULL */, float* out, int B, int U,
+                         int C, int H, int W, int mode, void* stream);
 
 /* ---- VAE decoder pieces (AutoencoderKL.decode, the step right after the sampling path) --------
  * idf_softmax_rows: p[r][0:n] = softmax(scale * s[r][0:n]) for `rows` stacked rows (row r at s + r*lds / p + r*ldp);

@@ -30,7 +30,7 @@ import torch
 
 from instancediffusion_amd.host.alpha import alpha_generator, set_alpha_scale
 from instancediffusion_amd.host.config import instantiate_from_config, load_yaml
-from instancediffusion_amd.host.input import meta_from_demo_json, prepare_batch, prepare_instance_meta
+from instancediffusion_amd.host.input import meta_from_demo_json, prepare_batch, prepare_instance_meta, prepare_layout_inputs
 from instancediffusion_amd.host.samplers import DDIMSampler, PLMSSampler, PLMSSamplerInst
 
 MAX_OBJS = 30
@@ -117,22 +117,91 @@ def latent_mask(path: str, size: int) -> torch.Tensor:
     return -torch.nn.functional.max_pool2d(-keep[None, None], 8)
 
 
-def clip_scores(args, images: torch.Tensor, data: dict, dtype) -> dict:
+def clip_scores(args, images: torch.Tensor, data: dict, dtype, input_json=None, loaded=None) -> dict:
     """``--clip_score``: the local CLIP score (host/clip_score.py) of every instance of every decoded image, straight from the fp32
     decoder output -- on backend ``hip`` the pixels never leave the device (``idf_clip_crop_resize`` quantises them as
     ``save_images`` does).  -> the content of ``clip_scores.json``."""
     from instancediffusion_amd.host import clip_score as cs
     boxes, phrases = cs.instances_from_demo_json(data)
-    model, tokenize, tokenizer = cs.load_clip(args.clip_path)
-    scorer = cs.InstanceClipScorer(model.to(images.device), tokenize, backend=args.clip_score, dtype=dtype)
+    if loaded is None or "scorer" not in loaded:                  # ``loaded``: a dict that keeps the model over several layouts
+        model, tokenize, tokenizer = cs.load_clip(args.clip_path)
+        scorer = cs.InstanceClipScorer(model.to(images.device), tokenize, backend=args.clip_score, dtype=dtype)
+        if loaded is not None:
+            loaded.update(scorer=scorer, tokenizer=tokenizer)
+    else:
+        scorer, tokenizer = loaded["scorer"], loaded["tokenizer"]
     scores = scorer.score_batch(images.float(), boxes, phrases)
     means, ranking = cs.rank_by_mean(scores)
-    return dict(metric="local CLIP score (eval_attribute_binding.py, HF branch)", input_json=args.input_json, backend=args.clip_score,
+    return dict(metric="local CLIP score (eval_attribute_binding.py, HF branch)", input_json=input_json or args.input_json, backend=args.clip_score,
                 dtype=args.dtype if args.clip_score == "hip" else "fp32", tokenizer=tokenizer,
                 weights=args.clip_path or "synthetic", phrases=phrases,
                 images={str(i): [round(v, 6) for v in s] for i, s in enumerate(scores)},
                 means={str(i): round(m, 6) for i, m in enumerate(means)}, ranking=ranking,
                 mean=round(sum(means) / len(means), 6))
+
+
+def layout_folders(paths) -> list:
+    """Output folder name per input JSON: its stem; a stem seen before gets a numeric suffix (a.json, x/a.json -> a, a_2)."""
+    seen, out = {}, []
+    for p in paths:
+        stem = os.path.splitext(os.path.basename(p))[0]
+        seen[stem] = seen.get(stem, 0) + 1
+        out.append(stem if seen[stem] == 1 else f"{stem}_{seen[stem]}")
+    return out
+
+
+def run_layouts(args, paths, model, autoencoder, diffusion, gi, text_encoder, phrase_encoder, dev, dtype):
+    """Several ``--input_json``: different layouts, ``--num_images`` images each, sampled in ONE batch (``sample_layouts``; with
+    ``--mis 0`` one row-stacked ``PLMSSampler`` / ``DDIMSampler`` call).  Every layout gets the starting noise a single-JSON run
+    with the same ``--seed`` draws, the negative prompt is shared, and layout l is written to
+    OUTPUT/<save_folder_name>/<json stem>/ with its own ``latents.pt`` / ``clip_scores.json``; ``--keep_best`` applies per layout."""
+    datas = [json.load(open(p)) for p in paths]
+    save_folder_name = f"gc{args.guidance_scale}-seed{args.seed}-alpha{args.alpha}"
+    metas = [meta_from_demo_json(d, args.alpha, ckpt=args.ckpt, save_folder_name=save_folder_name) for d in datas]
+    torch.manual_seed(args.seed)
+    starting_noise = torch.randn(args.num_images, 4, model.image_size, model.image_size).to(dev)
+    noises = [starting_noise] * len(paths)
+    uc = text_encoder.encode([args.negative_prompt if args.negative_prompt is not None else ""]).to(dev)
+    ag = partial(alpha_generator, type=metas[0]["alpha_type"])
+    K = args.num_images
+    if args.mis > 0:
+        sampler = PLMSSamplerInst(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale, mis=args.mis)
+        layouts = prepare_layout_inputs(metas, noises, gi, text_encoder, phrase_encoder, instances=True, max_objs=MAX_OBJS, device=dev)
+        try:
+            samples = sampler.sample_layouts(S=args.steps, layouts=layouts, uc=uc, guidance_scale=args.guidance_scale)
+        except ValueError as e:
+            raise SystemExit(str(e))
+    else:
+        inp = prepare_layout_inputs(metas, noises, gi, text_encoder, phrase_encoder, instances=False, max_objs=MAX_OBJS, device=dev)
+        n = K * len(paths)
+        extra = {}
+        if args.sampler == "ddim":
+            sampler = DDIMSampler(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale)
+            extra["eta"] = args.ddim_eta or 0.
+        else:
+            sampler = PLMSSampler(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale)
+        samples = sampler.sample(S=args.steps, shape=(n, model.in_channels, model.image_size, model.image_size), input=inp,
+                                 uc=uc.expand(n, -1, -1), guidance_scale=args.guidance_scale, **extra)
+    loaded = {}
+    for l, (path, stem) in enumerate(zip(paths, layout_folders(paths))):
+        lat = samples[l * K:(l + 1) * K]
+        images = autoencoder.decode(lat)
+        folder = os.path.join(args.output, save_folder_name, stem)
+        report = None
+        if args.clip_score:
+            report = clip_scores(args, images, datas[l], dtype, input_json=path, loaded=loaded)
+            if args.keep_best is not None:
+                images = images[report["ranking"][:args.keep_best]]
+        names = save_images(images, folder)
+        if report is not None:
+            kept = report["ranking"][:args.keep_best] if args.keep_best is not None else list(range(len(names)))
+            report["saved"] = {os.path.basename(n): i for n, i in zip(names, kept)}
+            with open(os.path.join(folder, "clip_scores.json"), "w") as f:
+                f.write(json.dumps(report, indent=1) + "\n")
+        if args.save_latents:
+            torch.save(dict(latents=lat.cpu(), caption=datas[l]["caption"], phrases=metas[l]["phrases"]),
+                       os.path.join(folder, "latents.pt"))
+        print(f"saved {len(names)} images {tuple(images.shape[1:])} to {folder}")
 
 
 def main():
@@ -142,7 +211,9 @@ def main():
     ap.add_argument("--guidance_scale", type=float, default=7.5)
     ap.add_argument("--negative_prompt", type=str, default="longbody, lowres, bad anatomy, bad hands, missing fingers, "
                     "extra digit, fewer digits, cropped, worst quality, low quality")
-    ap.add_argument("--input_json", type=str, default="demos/demo_four_boxes.json")
+    ap.add_argument("--input_json", type=str, nargs="+", default=["demos/demo_four_boxes.json"],
+                    help="one demo JSON, or several: different layouts sampled in ONE batch (--num_images each), written to "
+                         "OUTPUT/<save_folder_name>/<json stem>/")
     ap.add_argument("--ckpt", type=str, default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--alpha", type=float, default=0.75)
@@ -176,6 +247,14 @@ def main():
     ap.add_argument("--inpaint_mask", type=str, default=None,
                     help="inpainting: grey-scale PNG of the sampled size, >= 128 keeps the original, < 128 is repainted")
     args = ap.parse_args()
+    paths = list(args.input_json)
+    if len(paths) > 1:
+        if args.init_image is not None or args.inpaint_mask is not None:
+            raise SystemExit("inpainting (--init_image / --inpaint_mask) takes one --input_json")
+        if args.use_masked_att:
+            raise SystemExit("--use_masked_att takes one --input_json: the mask / no-mask decision is per layout call")
+    else:
+        args.input_json = paths[0]                                         # one path: exactly the single-layout run
     if args.sampler == "ddim" and args.mis > 0:
         raise SystemExit("--sampler ddim has no Multi-instance Sampler (the reference has none): give --mis 0")
     if args.ddim_eta is not None and args.sampler != "ddim":
@@ -230,6 +309,8 @@ def main():
     text_encoder = clip_text if use_clip else SyntheticTextEncoder()
     phrase_encoder = ClipPhraseEncoder(clip_text) if use_clip else text_encoder
 
+    if len(paths) > 1:
+        return run_layouts(args, paths, model, autoencoder, diffusion, gi, text_encoder, phrase_encoder, dev, dtype)
     data = json.load(open(args.input_json))
     save_folder_name = f"gc{args.guidance_scale}-seed{args.seed}-alpha{args.alpha}"
     meta = meta_from_demo_json(data, args.alpha, ckpt=args.ckpt, save_folder_name=save_folder_name)

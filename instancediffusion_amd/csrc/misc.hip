@@ -361,6 +361,77 @@ __global__ void mis_merge_kernel(const float* __restrict__ lat, const int* __res
   }
 }
 
+// mis_merge_kernel over a ragged unit list: image b owns the units unit_off[b] .. unit_off[b+1]-1 of lat [U][CHW], the first of
+// them its global trajectory.  Same operations in the same order as above (mode 0: s = 0, s += lat[k] in unit order, s / count;
+// mode 1: the global unit, then every later unit's box, later units win).  One thread per V consecutive elements of one image
+// (V == 4: CHW % 4 == 0, so a vector never crosses an image).  Every offset loaded from the table is clamped to [0, U]: a wrong
+// table cannot send a load outside lat (or boxes); an image left without units is written as zeros.
+template <int V>
+__global__ void mis_merge_ragged_kernel(const float* __restrict__ lat, const int* __restrict__ unit_off, const int* __restrict__ boxes,
+                                        float* __restrict__ out, int B, int U, long long CHW, int H, int W, int mode) {
+  static_assert(V == 1 || V == 4, "scalar or 16-B accesses");
+  const long long per = CHW / V;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)B * per) return;
+  const int b = (int)(i / per);
+  const long long e = (i - (long long)b * per) * V;                  // first element inside the image
+  const int k0 = min(max(unit_off[b], 0), U), k1 = min(max(unit_off[b + 1], 0), U);
+  float v[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) v[j] = 0.f;
+  auto load = [&](int k, float* dst) {
+    const float* p = lat + (long long)k * CHW + e;
+    if constexpr (V == 4) {
+      const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) dst[j] = t[j];
+    } else {
+      dst[0] = p[0];
+    }
+  };
+  if (k1 > k0) {
+    if (mode == 0) {
+      for (int k = k0; k < k1; ++k) {
+        float t[V];
+        load(k, t);
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[j] += t[j];
+      }
+      const float cnt = (float)(k1 - k0);
+#pragma unroll
+      for (int j = 0; j < V; ++j) v[j] = v[j] / cnt;                 // torch.mean(torch.stack(...), 0)
+    } else {
+      load(k0, v);
+      int h[V], w[V];
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const long long pix = (e + j) % ((long long)H * W);
+        h[j] = (int)(pix / W);
+        w[j] = (int)(pix % W);
+      }
+      for (int k = k0 + 1; k < k1; ++k) {                            // later units overwrite earlier ones (plms_instance.py:131-132)
+        const int* bb = boxes + 4 * (long long)k;
+        const int b0 = bb[0], b1 = bb[1], b2 = bb[2], b3 = bb[3];
+        bool in[V], any = false;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          // reference slices dim-2 (h) with bbox[0]:bbox[2] and dim-3 (w) with bbox[1]:bbox[3]
+          in[j] = h[j] >= b0 && h[j] < b2 && w[j] >= b1 && w[j] < b3;
+          any = any || in[j];
+        }
+        if (!any) continue;
+        float t[V];
+        load(k, t);
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[j] = in[j] ? t[j] : v[j];
+      }
+    }
+  }
+  float* o = out + (long long)b * CHW + e;
+  if constexpr (V == 4) *reinterpret_cast<f32x4*>(o) = f32x4{v[0], v[1], v[2], v[3]};
+  else o[0] = v[0];
+}
+
 template <int DT>
 __global__ void cast_kernel(const float* __restrict__ x, unsigned short* __restrict__ out, long long n) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -607,6 +678,21 @@ extern "C" int idf_mis_merge(const float* lat, const int* boxes, float* out, int
   if (mode == 1 && !boxes) return IDF_E_ARG;
   const long long per = (long long)B * C * H * W;
   hipLaunchKernelGGL(mis_merge_kernel, grid1d(per), dim3(256), 0, (hipStream_t)stream, lat, boxes, out, n_inst, B, C, H, W, mode);
+  return idf_launch_status();
+}
+
+extern "C" int idf_mis_merge_ragged(const float* lat, const int* unit_off, const int* boxes, float* out, int B, int U, int C, int H,
+                                    int W, int mode, void* stream) {
+  if (!lat || !unit_off || !out || B < 1 || U < B || C <= 0 || H <= 0 || W <= 0 || (mode != 0 && mode != 1)) return IDF_E_ARG;
+  if (mode == 1 && !boxes) return IDF_E_ARG;
+  const long long CHW = (long long)C * H * W;
+  hipStream_t s = (hipStream_t)stream;
+  // 16-B accesses: every pointer aligned and whole vectors inside every unit (the policy of idf_ddim_update)
+  const bool v4 = (CHW % 4) == 0 && aligned16(lat) && aligned16(out);
+  if (v4) hipLaunchKernelGGL(mis_merge_ragged_kernel<4>, grid1d((long long)B * (CHW / 4)), dim3(256), 0, s, lat, unit_off, boxes, out,
+                             B, U, CHW, H, W, mode);
+  else hipLaunchKernelGGL(mis_merge_ragged_kernel<1>, grid1d((long long)B * CHW), dim3(256), 0, s, lat, unit_off, boxes, out, B, U,
+                          CHW, H, W, mode);
   return idf_launch_status();
 }
 

@@ -184,6 +184,61 @@ def prepare_instance_meta(test_info, i, file_name=None, save_folder_name=None, c
     }
 
 
+@torch.no_grad()
+def prepare_layout_inputs(metas, starting_noises, grounding_input, text_encoder, phrase_model, processor=None, instances=True,
+                          max_objs=30, device="cuda"):
+    """A batch of DIFFERENT layouts for one sampler call, from their metas (``meta_from_demo_json``) and start latents
+    (``starting_noises[l]``: [K_l, 4, H, W], the K_l images of layout l).  ``text_encoder.encode(prompts) -> [n, 77, 768]``,
+    ``phrase_model`` / ``processor`` as in ``prepare_batch``, ``grounding_input``: the model's ``GroundingNetInput``.
+
+    ``instances=True`` (Multi-instance Sampler): the ``layouts`` argument of ``PLMSSamplerInst.sample_layouts`` -- per layout the
+    list [global, instance 1, .., instance N_l] of input dicts, conditioning at batch 1 (``prepare_batch`` on the meta, and on
+    ``prepare_instance_meta(meta, i)`` per instance), ``x`` the layout's start latents, shared by its dicts.
+    ``instances=False`` (``mis == 0``): ONE ordinary ``PLMSSampler`` / ``DDIMSampler`` input whose rows differ -- layout l's K_l
+    rows are ``prepare_batch(meta_l, batch=K_l)``, stacked layout after layout.
+
+    All-zero ``segs`` (30 x 512 x 512 fp32 = 31 MB per stack) are never copied: every all-zero stack of the call is ONE zero plane
+    set, and the rows of the stacked input broadcast it with a stride-0 view."""
+    image_size = int(starting_noises[0].shape[-1])
+    zero_plane = {}
+
+    def shared_zero(segs):
+        """segs [b, max_objs, S, S] -> the call's one zero plane set, broadcast over b, when all of it is zero."""
+        if bool(segs[:1].any()) if segs.stride(0) == 0 else bool(segs.any()):
+            return segs
+        key = (tuple(segs.shape[1:]), segs.dtype, segs.device)
+        if key not in zero_plane:
+            zero_plane[key] = torch.zeros((1,) + key[0], dtype=segs.dtype, device=segs.device)
+        return zero_plane[key].expand(segs.shape[0], -1, -1, -1)
+
+    def one(meta, batch, x):
+        b = prepare_batch(meta, batch=batch, max_objs=max_objs, model=phrase_model, processor=processor, image_size=image_size,
+                          device=device)
+        b["segs"] = shared_zero(b["segs"])
+        return dict(x=x, timesteps=None, context=text_encoder.encode([meta["prompt"]] * batch).to(device),
+                    grounding_input=grounding_input.prepare(b))
+
+    if instances:
+        layouts = []
+        for meta, x in zip(metas, starting_noises):
+            lay = [one(meta, 1, x)]
+            for i in range(len(meta["phrases"])):
+                lay.append(one(prepare_instance_meta(meta, i), 1, x))
+            layouts.append(lay)
+        return layouts
+    rows = [one(meta, int(x.shape[0]), x) for meta, x in zip(metas, starting_noises)]
+    g = {k: torch.cat([r["grounding_input"][k] for r in rows], 0) for k in rows[0]["grounding_input"] if k != "segs"}
+    segs = [r["grounding_input"]["segs"] for r in rows]
+    n = sum(int(s.shape[0]) for s in segs)
+    zeros = {z.data_ptr() for z in zero_plane.values()}
+    if all(s.data_ptr() in zeros and s.data_ptr() == segs[0].data_ptr() for s in segs):
+        g["segs"] = segs[0][:1].expand(n, -1, -1, -1)                     # one plane set for every row
+    else:
+        g["segs"] = torch.cat(segs, 0)
+    return dict(x=torch.cat(list(starting_noises), 0), timesteps=None, context=torch.cat([r["context"] for r in rows], 0),
+                grounding_input=g)
+
+
 def convert_points(points: List[float], img_info: Dict[str, int]) -> List[float]:
     """utils/input.py:152-159: absolute [x0,y0,x1,y1,...] -> relative, clipped at 1."""
     for i in range(len(points)):

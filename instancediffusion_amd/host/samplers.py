@@ -220,6 +220,88 @@ class PLMSSamplerInst(_PLMSBase):
             on = False
         return (dist, dist.get_rank(), dist.get_world_size()) if on else (None, 0, 1)
 
+    # ---- the two phases over a list of work units (shared by ``plms_sampling`` and ``sample_layouts``) ----------------
+    # A unit is any hashable key; the caller says where its conditioning lives (``row_of[u]``: bank row), which image it
+    # belongs to (``img_of(u)``: index into the stacked start latents, key of ``row_unc``) and where its start latent is (``x_of(u)``).
+    def _rows(self, units, row_of, row_unc, img_of, guided):
+        """Bank rows of a [cond | uncond] forward over ``units``."""
+        r = [row_of[u] for u in units]
+        if guided:
+            r += [row_unc[img_of(u)] for u in units]
+        return torch.tensor(r, device=self.engine.device, dtype=torch.long)
+
+    def _phase1(self, bank, chunks, units, row_of, row_unc, img_of, x_of, x_start, alphas, time_range, total, mis_step, guided,
+                guidance_scale, per_fwd):
+        """Advance every unit of ``chunks`` through the first ``mis_step`` steps, one batched forward per chunk and evaluation.
+        ``x_start`` (the start latents of all images, [n_img, 4, H, W] on the device) asks for the hoisted first evaluation, None
+        for none.  Returns ({unit: latent}, {unit: eps history})."""
+        eng = self.engine
+        ops = eng.ops
+        dev = eng.device
+        x_units: Dict[tuple, torch.Tensor] = {}
+        eps_units: Dict[tuple, list] = {}
+        # Exact hoist of the very first evaluation: every instance trajectory of image b still holds the SAME latent (the
+        # shared starting noise, inference.py:300-301) and the unconditional branch sees only (x, t, uc, null grounding),
+        # so it is identical for the N+1 instances of an image.  Evaluate all conditional rows of this rank's units plus
+        # ONE unconditional row per image up front, in full-width forwards, instead of one unconditional row per unit.
+        first_idx: Dict[tuple, int] = {}
+        first_unc: Dict[int, int] = {}
+        E_first = None
+        if x_start is not None:
+            self._apply_alpha(alphas, 0)
+            imgs = sorted({img_of(u) for u in units})
+            row_ids = [row_of[u] for u in units] + [row_unc[b] for b in imgs]
+            row_img = [img_of(u) for u in units] + imgs
+            first_idx = {u: k for k, u in enumerate(units)}
+            first_unc = {b: len(units) + k for k, b in enumerate(imgs)}
+            width = 2 * per_fwd
+            parts = []
+            for k in range(0, len(row_ids), width):
+                r = torch.tensor(row_ids[k:k + width], device=dev, dtype=torch.long)
+                xx = x_start[torch.tensor(row_img[k:k + width], device=dev, dtype=torch.long)]
+                tt = torch.full((xx.shape[0],), float(time_range[0]), device=dev, dtype=torch.float32)
+                slot = eng.gather_cond(bank, r)
+                parts.append(eng.forward_cond(xx, tt, slot, out=eng.buf("smp.eps_first", xx.shape, torch.float32)).clone())
+            E_first = torch.cat(parts, 0)
+        for chunk in chunks:
+            if not chunk:
+                continue
+            n = len(chunk)
+            pair = None
+            x = torch.stack([x_of(u) for u in chunk]).to(dev, torch.float32)
+            old: list = []
+            for i, step in enumerate(time_range[:mis_step]):
+                self._apply_alpha(alphas, i)
+                index = total - i - 1
+                step_next = int(time_range[min(i + 1, len(time_range) - 1)])
+                e_first = None
+                if i == 0 and E_first is not None:
+                    ic = torch.tensor([first_idx[u] for u in chunk], device=dev, dtype=torch.long)
+                    iu = torch.tensor([first_unc[img_of(u)] for u in chunk], device=dev, dtype=torch.long)
+                    e_first = ops.cfg_combine(E_first[ic].contiguous(), E_first[iu].contiguous(), guidance_scale,
+                                              ops.empty(x.shape, torch.float32))
+                if i == 0 or pair is None:
+                    pair = eng.gather_cond(bank, self._rows(chunk, row_of, row_unc, img_of, guided))
+                x, e_t = self._plms_step(x, old, index, int(step), step_next, pair, n, guided, guidance_scale,
+                                         e_t_first=e_first)
+                self._push(old, e_t)
+            for k, u in enumerate(chunk):
+                x_units[u] = x[k]
+                eps_units[u] = [e[k] for e in old]
+        return x_units, eps_units
+
+    def _phase2(self, x, old, pair, n, alphas, time_range, total, mis_step, guided, guidance_scale):
+        """The shared trajectory from step ``mis_step`` on (plms_instance.py:138-156): n rows, ``old`` = their eps history."""
+        for i, step in enumerate(time_range):
+            if i < mis_step:
+                continue
+            self._apply_alpha(alphas, i)
+            index = total - i - 1
+            step_next = int(time_range[min(i + 1, len(time_range) - 1)])
+            x, e_t = self._plms_step(x, old, index, int(step), step_next, pair, n, guided, guidance_scale)
+            self._push(old, e_t)
+        return x
+
     @torch.no_grad()
     def plms_sampling(self, shape, input_all, uc=None, guidance_scale=1, mask=None, x0=None):
         eng = self.engine
@@ -304,11 +386,11 @@ class PLMSSamplerInst(_PLMSBase):
         parts = conds + ([cond_u] if cond_u is not None else [])
         bank = type(parts[0]).cat(parts) if parts else None
 
+        def img_of(u):
+            return u[1]
+
         def rows(units):
-            r = [row_of[u] for u in units]
-            if guided:
-                r += [row_unc[b] for (_, b) in units]
-            return torch.tensor(r, device=dev, dtype=torch.long)
+            return self._rows(units, row_of, row_unc, img_of, guided)
 
         # Reference quirk: restore_first_conv_from_SD is never undone, so if alpha hits 0 inside phase 1 the LATER
         # instances would run their EARLY steps with the swapped conv.  Only then is the serial order observable;
@@ -322,58 +404,11 @@ class PLMSSamplerInst(_PLMSBase):
             for n in self.chunk_sizes(len(units), per_fwd):
                 chunks.append(units[k:k + n])
                 k += n
-        x_units: Dict[tuple, torch.Tensor] = {}
-        eps_units: Dict[tuple, list] = {}
         same_start = all(inp["x"] is input_all[0]["x"] or torch.equal(inp["x"], input_all[0]["x"]) for inp in input_all[1:])
-        # Exact hoist of the very first evaluation: every instance trajectory of image b still holds the SAME latent (the
-        # shared starting noise, inference.py:300-301) and the unconditional branch sees only (x, t, uc, null grounding),
-        # so it is identical for the N+1 instances of an image.  Evaluate all conditional rows of this rank's units plus
-        # ONE unconditional row per image up front, in full-width forwards, instead of one unconditional row per unit.
-        first_idx: Dict[tuple, int] = {}
-        first_unc: Dict[int, int] = {}
-        E_first = None
-        if guided and same_start and units and mis_step > 0 and not serial:
-            self._apply_alpha(alphas, 0)
-            imgs = sorted({b for (_, b) in units})
-            row_ids = [row_of[u] for u in units] + [row_unc[b] for b in imgs]
-            row_img = [b for (_, b) in units] + imgs
-            first_idx = {u: k for k, u in enumerate(units)}
-            first_unc = {b: len(units) + k for k, b in enumerate(imgs)}
-            x0_all = input_all[0]["x"].to(dev, torch.float32)
-            width = 2 * per_fwd
-            parts = []
-            for k in range(0, len(row_ids), width):
-                r = torch.tensor(row_ids[k:k + width], device=dev, dtype=torch.long)
-                xx = x0_all[torch.tensor(row_img[k:k + width], device=dev, dtype=torch.long)]
-                tt = torch.full((xx.shape[0],), float(time_range[0]), device=dev, dtype=torch.float32)
-                slot = eng.gather_cond(bank, r)
-                parts.append(eng.forward_cond(xx, tt, slot, out=eng.buf("smp.eps_first", xx.shape, torch.float32)).clone())
-            E_first = torch.cat(parts, 0)
-        for chunk in chunks:
-            if not chunk:
-                continue
-            n = len(chunk)
-            pair = None
-            x = torch.stack([input_all[j]["x"][b] for (j, b) in chunk]).to(dev, torch.float32)
-            old: list = []
-            for i, step in enumerate(time_range[:mis_step]):
-                self._apply_alpha(alphas, i)
-                index = total - i - 1
-                step_next = int(time_range[min(i + 1, len(time_range) - 1)])
-                e_first = None
-                if i == 0 and E_first is not None:
-                    ic = torch.tensor([first_idx[u] for u in chunk], device=dev, dtype=torch.long)
-                    iu = torch.tensor([first_unc[b] for (_, b) in chunk], device=dev, dtype=torch.long)
-                    e_first = ops.cfg_combine(E_first[ic].contiguous(), E_first[iu].contiguous(), guidance_scale,
-                                              ops.empty(x.shape, torch.float32))
-                if i == 0 or pair is None:
-                    pair = eng.gather_cond(bank, rows(chunk))
-                x, e_t = self._plms_step(x, old, index, int(step), step_next, pair, n, guided, guidance_scale,
-                                         e_t_first=e_first)
-                self._push(old, e_t)
-            for k, u in enumerate(chunk):
-                x_units[u] = x[k]
-                eps_units[u] = [e[k] for e in old]
+        hoist = bool(guided and same_start and units and mis_step > 0 and not serial)
+        x_units, eps_units = self._phase1(bank, chunks, units, row_of, row_unc, img_of, lambda u: input_all[u[0]]["x"][u[1]],
+                                          input_all[0]["x"].to(dev, torch.float32) if hoist else None, alphas, time_range, total,
+                                          mis_step, guided, guidance_scale, per_fwd)
 
         # ---------------- merge (plms_instance.py:128-135) ------------------------------------------------------
         # The SAME arithmetic at every world size: the N+1 unit latents of every image are laid out in the fixed order
@@ -417,15 +452,7 @@ class PLMSSamplerInst(_PLMSBase):
             old = [torch.stack([eps_units[(0, b)][k] for b in mine]) for k in range(len(eps_units[(0, mine[0])]))] \
                 if mis_step > 0 else []
             pair = eng.gather_cond(bank, rows([(0, b) for b in mine]))
-            for i, step in enumerate(time_range):
-                if i < mis_step:
-                    continue
-                self._apply_alpha(alphas, i)
-                index = total - i - 1
-                step_next = int(time_range[min(i + 1, len(time_range) - 1)])
-                x, e_t = self._plms_step(x, old, index, int(step), step_next, pair, n, guided, guidance_scale)
-                self._push(old, e_t)
-            out[idx] = x
+            out[idx] = self._phase2(x, old, pair, n, alphas, time_range, total, mis_step, guided, guidance_scale)
         if dist is not None:
             # finished images of every rank, again as an all-gather of what each rank owns (images b = r, r + W, ...)
             cap = (B + world - 1) // world
@@ -440,6 +467,163 @@ class PLMSSamplerInst(_PLMSBase):
                     out[torch.tensor(theirs, device=dev)] = recv[r][:len(theirs)]
         input_all[0]["x"] = out
         return out
+
+    # ---- a batch of DIFFERENT layouts in one call -------------------------------------------------------------------
+    SEG_ROWS_PER_PREPARE = 8            # rows with a real mask stack (31 MB each at 30 x 512^2) per prepare_cond call
+
+    def _stack_conds(self, inputs):
+        """One conditioning row per batch-1 input dict, in the order given, built with FEW ``prepare_cond`` calls over stacked
+        rows: every row whose ``segs`` are all zero goes into one call, with one zero plane set broadcast over the rows (a
+        stride-0 view, as ``host/input.py`` and ``get_null_input`` hand it out); rows with a real mask stack follow
+        SEG_ROWS_PER_PREPARE at a time.  Returns (Cond, bank row of every input)."""
+        eng = self.engine
+        dev = eng.device
+        gi = self.model.grounding_tokenizer_input
+        rows, zero_of = [], {}
+        for inp in inputs:
+            g = inp["grounding_input"] if "grounding_input" in inp else gi.get_null_input(batch=1)
+            if inp["context"].shape[0] != 1 or g["boxes"].shape[0] != 1:
+                raise ValueError("sample_layouts: every input dict holds its conditioning at batch 1")
+            segs = g["segs"]
+            if id(segs) not in zero_of:
+                zero_of[id(segs)] = not bool(segs[:1].any())
+            rows.append((inp["context"], g, zero_of[id(segs)]))
+
+        def points(g):
+            p = g.get("points")
+            return ((g["boxes"][..., :2] + g["boxes"][..., 2:]) / 2.0) if p is None else p
+
+        def prepare(sel, segs):
+            ctx = torch.cat([rows[r][0].to(dev) for r in sel], 0)
+            g = {k: torch.cat([rows[r][1][k].to(dev) for r in sel], 0)
+                 for k in ("boxes", "masks", "positive_embeddings", "scribbles", "polygons")}
+            g["points"] = torch.cat([points(rows[r][1]).to(dev) for r in sel], 0)
+            g["segs"] = segs
+            return eng.prepare_cond(ctx, g)
+
+        seg_shape = rows[0][1]["segs"].shape[1:]
+        zero = [r for r, (_, g, z) in enumerate(rows) if z and g["segs"].shape[1:] == seg_shape]
+        real = [r for r in range(len(rows)) if r not in set(zero)]
+        parts, order = [], []
+        if zero:
+            plane = rows[zero[0]][1]["segs"][:1].to(dev)
+            parts.append(prepare(zero, plane.expand(len(zero), *seg_shape)))
+            order += zero
+        for k in range(0, len(real), self.SEG_ROWS_PER_PREPARE):
+            sel = real[k:k + self.SEG_ROWS_PER_PREPARE]
+            parts.append(prepare(sel, torch.cat([rows[r][1]["segs"][:1].to(dev) for r in sel], 0)))
+            order += sel
+        bank = type(parts[0]).cat(parts) if len(parts) > 1 else parts[0]
+        where = {r: k for k, r in enumerate(order)}
+        return bank, [where[r] for r in range(len(rows))]
+
+    @torch.no_grad()
+    def sample_layouts(self, S, layouts, uc=None, guidance_scale=1):
+        """One call for L DIFFERENT layouts with different instance counts, their work units packed into the same wide forwards
+        ``sample()`` forms from copies of one layout.
+
+        ``layouts[l]`` is the ``input_all`` list of layout l, ``[global, instance 1, .., instance N_l]`` with N_l >= 0: every dict
+        holds its conditioning (``context``, ``grounding_input``) at batch 1 and ``x`` [K_l, 4, H, W], the start latents of that
+        layout's K_l images, shared by the layout's dicts.  ``uc``: one row for all, or one row per layout.  Returns
+        [sum K_l, 4, H, W], layout after layout; image k of layout l is what ``sample(S, (1, 4, H, W), layouts[l] with x[k:k+1],
+        uc_l, guidance_scale)`` returns as the first call on a freshly loaded model (the first-conv swap happens at the same
+        step for every row, so this holds for all layouts at once).  The input dicts are left as they are.
+
+        Execution: the two phases of ``plms_sampling`` over the ragged unit list (layout, instance, image), chunked by
+        ``units_per_forward`` / ``chunk_sizes``; the hoisted first evaluation keeps one unconditional row per image; conditioning is
+        prepared once per LAYOUT and shared by its images through bank row indices; the merge is ONE ``idf_mis_merge_ragged`` call.
+        Runs on this process's GPU only: layout batches are NOT sharded over ranks, whatever ``shard_across_ranks`` says.
+
+        ValueError: a model built for masked gated self-attention (the mask / no-mask decision is per reference call), an alpha
+        schedule that reaches 0 inside phase 1 (the reference's serial-order quirk cannot be reproduced for independent layouts),
+        ``crop_and_paste_latents`` with a layout without instances."""
+        self.make_schedule(ddim_num_steps=S)
+        eng = self.engine
+        ops = eng.ops
+        dev = eng.device
+        if len(layouts) == 0 or any(len(lay) == 0 for lay in layouts):
+            raise ValueError("sample_layouts: needs at least one layout, and every layout at least its global input")
+        if eng.masked_fuser:
+            raise ValueError("sample_layouts: a model built for masked gated self-attention takes its mask / no-mask decision per "
+                             "reference call; use sample() per layout")
+        time_range = np.flip(self.ddim_timesteps)
+        total = self.ddim_timesteps.shape[0]
+        alphas = self.alpha_generator_func(len(time_range)) if self.alpha_generator_func is not None else None
+        mis_step = int(total * self.mis)
+        if alphas is not None and any(alphas[i] == 0 for i in range(mis_step)):
+            raise ValueError("sample_layouts: the alpha schedule reaches 0 inside phase 1; the reference then runs the instances "
+                             "in serial order with a swapped first conv, which independent layouts cannot reproduce")
+        n_inst = [len(lay) - 1 for lay in layouts]
+        if self.crop_and_paste_latents and min(n_inst) == 0:
+            raise ValueError("sample_layouts: crop_and_paste_latents needs at least one instance in every layout")
+        L = len(layouts)
+        xs = [lay[0]["x"] for lay in layouts]
+        if any(not torch.is_tensor(x) or x.dim() != 4 or x.shape[0] < 1 or x.shape[1:] != xs[0].shape[1:] for x in xs):
+            raise ValueError("sample_layouts: every layout carries its start latents x [K_l, 4, H, W], all of one size")
+        guided = uc is not None and guidance_scale != 1
+        if guided and uc.shape[0] not in (1, L):
+            raise ValueError(f"sample_layouts: uc has {uc.shape[0]} rows, expected 1 or one per layout ({L})")
+        self._check_first_conv(alphas)
+        K = [int(x.shape[0]) for x in xs]
+        base = [sum(K[:l]) for l in range(L)]
+        n_img = sum(K)
+        shape = (n_img,) + tuple(xs[0].shape[1:])
+        H, W = int(shape[2]), int(shape[3])
+
+        # ---------------- units, instance-major as in plms_sampling (a uniform layout list forms sample()'s forwards) -------
+        units = [(l, j, k) for j in range(max(n_inst) + 1) for l in range(L) if j <= n_inst[l] for k in range(K[l])]
+
+        def img_of(u):
+            return base[u[0]] + u[2]
+
+        # ---------------- conditioning bank: one row per (layout, input), one unconditional row per layout (or one for all) --
+        flat = [(l, j) for l in range(L) for j in range(n_inst[l] + 1)]
+        bank, where = self._stack_conds([layouts[l][j] for (l, j) in flat])
+        row_lj = {lj: where[k] for k, lj in enumerate(flat)}
+        row_of = {u: row_lj[(u[0], u[1])] for u in units}
+        row_unc: Dict[int, int] = {}
+        if guided:
+            uc_shared = uc.shape[0] == 1 or guided_uc_shared(uc)
+            off = bank.B
+            bank = type(bank).cat([bank, self._uncond(uc[:1] if uc_shared else uc)])
+            row_unc = {base[l] + k: off + (0 if uc_shared else l) for l in range(L) for k in range(K[l])}
+
+        # ---------------- phase 1 ---------------------------------------------------------------------------------------------
+        per_fwd = self.units_per_forward(self.max_units, H, W)
+        chunks, k0 = [], 0
+        for n in self.chunk_sizes(len(units), per_fwd):
+            chunks.append(units[k0:k0 + n])
+            k0 += n
+        same_start = all(inp["x"] is lay[0]["x"] or torch.equal(inp["x"], lay[0]["x"]) for lay in layouts for inp in lay[1:])
+        hoist = bool(guided and same_start and mis_step > 0)
+        x_start = torch.cat([x.to(dev, torch.float32) for x in xs], 0)
+        x_units, eps_units = self._phase1(bank, chunks, units, row_of, row_unc, img_of, lambda u: layouts[u[0]][u[1]]["x"][u[2]],
+                                          x_start if hoist else None, alphas, time_range, total, mis_step, guided, guidance_scale,
+                                          per_fwd)
+
+        # ---------------- merge: the unit latents image after image, an image's global unit first; ONE ragged launch ---------
+        by_img = [(l, j, k) for l in range(L) for k in range(K[l]) for j in range(n_inst[l] + 1)]
+        unit_off = [0]
+        for l in range(L):
+            for k in range(K[l]):
+                unit_off.append(unit_off[-1] + n_inst[l] + 1)
+        lat = torch.zeros((len(by_img),) + tuple(shape[1:]), device=dev, dtype=torch.float32)
+        for pos, u in enumerate(by_img):
+            if u in x_units:
+                lat[pos] = x_units[u]
+        if self.crop_and_paste_latents:
+            zero4 = [0, 0, 0, 0]
+            boxes = torch.tensor([zero4 if j == 0 else [int(v * H) for v in layouts[l][j]["grounding_input"]["boxes"][0][0].tolist()]
+                                  for (l, j, k) in by_img], dtype=torch.int32, device=dev).reshape(-1, 4)
+            merged = ops.mis_merge_ragged(lat, unit_off, boxes, ops.empty(shape, torch.float32), 1)
+        else:
+            merged = ops.mis_merge_ragged(lat, unit_off, None, ops.empty(shape, torch.float32), 0)
+
+        # ---------------- phase 2: one row per image, with the eps history of that image's global unit ------------------------
+        glob = [(l, 0, k) for l in range(L) for k in range(K[l])]
+        old = [torch.stack([eps_units[u][i] for u in glob]) for i in range(len(eps_units[glob[0]]))] if mis_step > 0 else []
+        pair = eng.gather_cond(bank, self._rows(glob, row_of, row_unc, img_of, guided))
+        return self._phase2(merged.contiguous(), old, pair, n_img, alphas, time_range, total, mis_step, guided, guidance_scale)
 
 
 class DDIMSampler(_PLMSBase):

@@ -522,6 +522,30 @@ class HipOps:
                                           self._stream()), "idf_mis_merge")
         return out
 
+    @staticmethod
+    def check_unit_offsets(unit_off, B, U):
+        """The offset table of ``mis_merge_ragged`` as a list of ints: B + 1 entries, starts at 0, strictly increasing (every image
+        owns at least its global unit), ends at U.  ValueError otherwise -- the kernel only clamps what it loads."""
+        off = [int(v) for v in (unit_off.tolist() if torch.is_tensor(unit_off) else unit_off)]
+        if len(off) != B + 1 or off[0] != 0 or off[-1] != U or any(b <= a for a, b in zip(off, off[1:])):
+            raise ValueError(f"mis_merge_ragged: unit offsets must be {B + 1} strictly increasing entries from 0 to {U}, got {off}")
+        return off
+
+    def mis_merge_ragged(self, lat, unit_off, boxes_i32, out, mode):
+        """``idf_mis_merge`` over a ragged unit list.  lat [U,C,H,W] fp32 (unit latents, image after image, an image's global unit
+        first), unit_off: B + 1 host ints (validated here, then uploaded), boxes_i32 [U,4] int32 on the device (mode 1) or None,
+        out [B,C,H,W]."""
+        U, Cc, H, W_ = lat.shape
+        B = out.shape[0]
+        assert lat.dtype == torch.float32 and out.dtype == torch.float32 and lat.is_contiguous() and out.is_contiguous()
+        assert tuple(out.shape[1:]) == (Cc, H, W_)
+        off = torch.tensor(self.check_unit_offsets(unit_off, B, U), dtype=torch.int32).to(self.device)
+        if boxes_i32 is not None:
+            assert boxes_i32.dtype == torch.int32 and boxes_i32.is_contiguous() and tuple(boxes_i32.shape) == (U, 4)
+        _lib.check(self.lib.idf_mis_merge_ragged(_p(lat), _p(off), _p(boxes_i32), _p(out), B, U, Cc, H, W_, int(mode),
+                                                 self._stream()), "idf_mis_merge_ragged")
+        return out
+
     def cast16(self, x_f32, out):
         assert x_f32.is_contiguous() and out.is_contiguous()
         _lib.check(self.lib.idf_cast_f32_to_16(_p(x_f32), _p(out), out.numel(), self.dt, self._stream()),
