@@ -858,9 +858,14 @@ class UNetEngine:
         return eps
 
     def _bind(self, cond: Cond) -> Cond:
-        """Copy ``cond`` into the static per-batch-size slot that captured graphs read (no-op if already bound)."""
+        """Copy ``cond`` into the static per-batch-size slot that captured graphs read (no-op if already bound).
+        The slot object itself (what ``gather_cond`` returned) is only valid until another conditioning of its batch size is
+        bound: after that it holds the other conditioning's values, so handing it in again is an error, not a forward."""
         B = cond.B
         slot = self._slots.get(B)
+        if cond is slot and self._slot_bound[B] != cond.uid:
+            raise RuntimeError(f"forward_cond: the static slot of batch size {B} (Cond uid {cond.uid}, from gather_cond) was "
+                               f"overwritten by Cond uid {self._slot_bound[B]} since it was gathered; call gather_cond again")
         if slot is None or not slot.same_layout(cond):
             slot = cond.clone()
             self._slots[B] = slot
@@ -875,7 +880,9 @@ class UNetEngine:
     def gather_cond(self, bank: Cond, idx: torch.Tensor) -> Cond:
         """Fill the static slot of batch size len(idx) with rows ``idx`` of ``bank`` (ONE gather per tensor, written
         in place) and return the slot; ``forward_cond(x, t, slot)`` then replays the captured graph without any further
-        conditioning copy.  Used by the samplers to assemble [cond | uncond] / per-unit batches."""
+        conditioning copy.  Used by the samplers to assemble [cond | uncond] / per-unit batches.  The returned handle is good
+        until another conditioning of that batch size is bound (a ``forward_cond`` / ``forward`` with another Cond of len(idx) rows):
+        the slot then holds that one, and ``forward_cond(x, t, slot)`` raises until ``gather_cond`` is called again."""
         B = int(idx.numel())
         slot = self._slots.get(B)
         if slot is None or len(slot._tensors()) != len(bank._tensors()) or any(
