@@ -16,51 +16,27 @@ Design, following ``vae_engine.py``:
 Nothing depends on the width or the depth beyond head dim 64 and C % 64 == 0.
 
 ``CLIPVisionEngine`` is the image tower (``CLIPModel.get_image_features`` of ``eval/eval_attribute_binding.py:19-60``) on the same
-code: weight packing, buffers and the layer loop live in ``_CLIPEngine``; the tower swaps ``idf_attention_causal`` for
+code: the per-layer weights and the layer loop live in ``_CLIPEngine``, packing primitives and buffers in ``EngineBase``; the tower swaps ``idf_attention_causal`` for
 ``idf_attention_qkv`` and the embedding gather for ``idf_clip_patchify`` + one batched GEMM.
 """
 from __future__ import annotations
 
-from typing import Dict
-
 import torch
 
-from .engine import _Lin
+from .engine_base import EngineBase
 
 
-class _CLIPEngine:
-    """What the two towers share: 16-bit weight packing with the LayerNorms folded in, static buffers, the encoder-layer loop."""
+class _CLIPEngine(EngineBase):
+    """What the two towers share on top of ``EngineBase`` (packing primitives with the LayerNorm fold, static buffers): the
+    per-layer weights and the encoder-layer loop.  The towers run eagerly: they capture no graph."""
 
     NAME = "CLIP engine"
 
     def __init__(self, ops=None, dtype: torch.dtype = torch.bfloat16):
-        if ops is None:
-            from .ops import HipOps          # raises when libidf_gfx950.so / the GPU is missing: no fallback
-            ops = HipOps(dtype)
-        self.ops = ops
-        self.dtype = ops.dtype
-        self.device = ops.device
+        super().__init__(ops, dtype, use_graphs=False)
         self.max_batch = 64
-        self._bufs: Dict[tuple, torch.Tensor] = {}
 
     # ---- weight packing ---------------------------------------------------------------------------------------
-    def _w16(self, t):
-        return t.detach().to(device=self.device, dtype=torch.float32).to(self.dtype).contiguous()
-
-    def _f32(self, t):
-        return t.detach().to(device=self.device, dtype=torch.float32).contiguous()
-
-    def _fold_ln(self, w, bias, norm):
-        """``engine.UNetEngine._fold_ln``: -> (16-bit gamma-folded weight, c = its row sums as the MFMA sees them,
-        d = W beta + bias)."""
-        w = w.detach().float()
-        g, b = norm.weight.detach().float(), norm.bias.detach().float()
-        w16 = self._w16(w * g[None, :])
-        return w16, w16.float().sum(1).contiguous(), self._f32(w @ b + bias.detach().float())
-
-    def _lin(self, m) -> _Lin:
-        return _Lin(self._w16(m.weight), self._f32(m.bias))
-
     def _pack_encoder(self, cfg, encoder):
         """The checks and the per-layer weights both towers need; sets C, heads, eps, layers, inter."""
         if cfg.hidden_act != "quick_gelu":
@@ -77,16 +53,6 @@ class _CLIPEngine:
             self.layers.append(dict(qkv=self._fold_ln(wqkv, bqkv, ly.layer_norm1), out=self._lin(a.out_proj),
                                     fc1=self._fold_ln(ly.mlp.fc1.weight, ly.mlp.fc1.bias, ly.layer_norm2), fc2=self._lin(ly.mlp.fc2)))
         self.inter = int(encoder.layers[0].mlp.fc1.weight.shape[0])
-
-    # ---- buffers ----------------------------------------------------------------------------------------------
-    def buf(self, role: str, shape, dtype=None) -> torch.Tensor:
-        dtype = dtype or self.dtype
-        key = (role, tuple(int(s) for s in shape), dtype)
-        t = self._bufs.get(key)
-        if t is None:
-            t = self.ops.empty(key[1], dtype)
-            self._bufs[key] = t
-        return t
 
     # ---- the encoder layers -------------------------------------------------------------------------------------
     def _run_layers(self, x, y, b, T, attention):

@@ -14,32 +14,14 @@ MI355X-first design decisions (vs the reference's PyTorch module tree):
 """
 from __future__ import annotations
 
-import contextlib
-import gc
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
+from .engine_base import EngineBase, _Lin, capture_graph, pack_conv3x3  # noqa: F401  (the names stay importable from here)
 from .host.attention import SpatialTransformer
 from .host.unet import Downsample, ResBlock, UNetModel, Upsample
-
-
-@contextlib.contextmanager
-def capture_graph(graph):
-    """``torch.cuda.graph(graph)`` with the cyclic garbage collector held off.  torch.cuda.graph no longer collects on entry, so a
-    dead cycle from earlier work (a dropped model with its engine, graphs and events) could be finalised between two captured
-    launches, and a finaliser that calls the runtime inside a capture aborts the process (seen in the GPU suite: ``Fatal Python
-    error: Aborted`` while garbage-collecting inside the capture of a sampler test).  Collect before, keep the collector out."""
-    gc.collect()
-    was_on = gc.isenabled()
-    gc.disable()
-    try:
-        with torch.cuda.graph(graph):
-            yield
-    finally:
-        if was_on:
-            gc.enable()
 
 
 # LayerNorm statistics of the folded GEMMs (A/B switch, env IDF_LN_SELF): 0 = every producer of the residual stream emits them
@@ -116,12 +98,6 @@ def pack_geglu(w: torch.Tensor, b: torch.Tensor, period: int = 64) -> Tuple[torc
     return torch.cat([wv, wg], dim=1).reshape(n2, k).contiguous(), torch.cat([bv, bg], dim=1).reshape(n2).contiguous()
 
 
-def pack_conv3x3(w: torch.Tensor) -> torch.Tensor:
-    """[Cout, Cin, 3, 3] -> [Cout, (ky*3+kx)*Cin + ci]  (K order of the implicit-GEMM gather)."""
-    co, ci = w.shape[0], w.shape[1]
-    return w.permute(0, 2, 3, 1).reshape(co, 9 * ci).contiguous()
-
-
 def pack_conv_up2x(w: torch.Tensor) -> torch.Tensor:
     """Nearest-x2 upsample folded into a 3x3 pad-1 conv: fp32 [Cout, Cin, 3, 3] -> fp32 [4, Cout, (ty*2+tx)*Cin + ci], one 2x2 conv on
     the LOW-resolution image per output parity phase, phases in the order (py, px) = (0,0), (0,1), (1,0), (1,1).  Output row 2y + py
@@ -141,13 +117,6 @@ def pack_conv_up2x(w: torch.Tensor) -> torch.Tensor:
                 taps += [cols[0], cols[1]]                     # (ty, tx = 0), (ty, tx = 1): [Cout, Cin] each
             out[py * 2 + px] = torch.stack(taps, dim=1).reshape(co, 4 * ci)
     return out
-
-
-class _Lin:
-    __slots__ = ("w", "b")
-
-    def __init__(self, w, b):
-        self.w, self.b = w, b
 
 
 class Cond:
@@ -206,14 +175,9 @@ class Cond:
         return out
 
 
-class UNetEngine:
+class UNetEngine(EngineBase):
     def __init__(self, model: UNetModel, ops=None, dtype: torch.dtype = torch.bfloat16, use_graphs: bool = True):
-        if ops is None:
-            from .ops import HipOps          # raises when libidf_gfx950.so / the GPU is missing: no fallback
-            ops = HipOps(dtype)
-        self.ops = ops
-        self.dtype = ops.dtype
-        self.device = ops.device
+        super().__init__(ops, dtype, use_graphs)
         self.model = model
         self.heads = model.num_heads
         self.masked_fuser = not getattr(model, "efficient_attention", True)     # attention.py:189
@@ -225,9 +189,6 @@ class UNetEngine:
         if self.vt_min_n < 64 or self.vt_min_n % 64:
             raise ValueError(f"IDF_VT_MIN_N={self.vt_min_n}: a positive multiple of 64 (tokens per sample from which the fused "
                              "q | k | v launch is used; default 256)")
-        self.use_graphs = use_graphs and self.device.type == "cuda"
-        self._bufs: Dict[tuple, torch.Tensor] = {}
-        self._graphs: Dict[tuple, tuple] = {}
         self._paired_checked: set = set()
         self._cond_cache: Dict[tuple, Cond] = {}
         self._slots: Dict[int, Cond] = {}                      # batch size -> static Cond the hipGraphs read from
@@ -237,23 +198,8 @@ class UNetEngine:
         self.set_fuser_scale(1.0)
 
     # =================================================================================================
-    # weight packing (once; HBM-resident 16-bit GEMM images + fp32 vectors)
+    # weight packing (once; the primitives -- _w16, _f32, _lin, _conv, _fold_ln, _conv_out_padded -- are EngineBase's)
     # =================================================================================================
-    def _w16(self, t: torch.Tensor) -> torch.Tensor:
-        return t.detach().to(device=self.device, dtype=torch.float32).to(self.dtype).contiguous()
-
-    def _f32(self, t: torch.Tensor) -> torch.Tensor:
-        return t.detach().to(device=self.device, dtype=torch.float32).contiguous()
-
-    def _lin(self, m, with_bias=True) -> _Lin:
-        w = m.weight
-        if w.dim() == 4:
-            w = w.reshape(w.shape[0], w.shape[1])            # 1x1 conv
-        return _Lin(self._w16(w), self._f32(m.bias) if (with_bias and m.bias is not None) else None)
-
-    def _conv(self, m) -> _Lin:
-        return _Lin(self._w16(pack_conv3x3(m.weight.detach().float())), self._f32(m.bias))
-
     def _pack_up(self, m) -> dict:
         """Upsample conv: the four folded 2x2 phase images (pack_conv_up2x) when the folded path is active, and then NOT the 3x3
         image -- ``_up_conv3`` packs that one on demand, for a forward whose shape the folded launch does not take."""
@@ -265,17 +211,6 @@ class UNetEngine:
         if p["conv"] is None:
             p["conv"] = self._conv(p["mod"])
         return p["conv"]
-
-    # LayerNorm -> Linear pairs are stored FOLDED (include/idf.h IDF_EPI_LN_ROW / LN_COL): the weight carries gamma,
-    #   LN(x) W^T = rstd * (x (gamma*W)^T - mu * c) + d,   c = row sums of the 16-bit (gamma*W),   d = W beta (+ bias),
-    # so the forward never materialises LN(x): a GEMM reads the raw residual stream and its epilogue applies (mu, rstd).
-    def _fold_ln(self, w: torch.Tensor, bias, norm):
-        """-> (16-bit gamma-folded weight, c [N] fp32 = its row sums as the MFMA sees them, d [N] fp32 = W beta + bias)."""
-        w = w.detach().float()
-        g, b = norm.weight.detach().float(), norm.bias.detach().float()
-        w16 = self._w16(w * g[None, :])
-        d = w @ b + (bias.detach().float() if bias is not None else 0.0)
-        return w16, w16.float().sum(1).contiguous(), self._f32(d)
 
     def _pack_ff(self, ff, norm):
         """GEGLU feed-forward behind LayerNorm `norm`: proj rows interleaved value | gate per GEGLU_PERIOD (pack_geglu), gamma folded."""
@@ -376,13 +311,8 @@ class UNetEngine:
             s = getattr(model, f"scaleu_s_{i}").detach().float()
             self.scaleu.append((self._f32(torch.tanh(b) + 1.0), self._f32(torch.tanh(s))))
         self.out_gn = (self._f32(model.out[0].weight), self._f32(model.out[0].bias))
-        oc = model.out[2]
-        wpad = torch.zeros(64, oc.weight.shape[1], 3, 3)
-        wpad[: oc.weight.shape[0]] = oc.weight.detach().float().cpu()
-        bpad = torch.zeros(64)
-        bpad[: oc.bias.shape[0]] = oc.bias.detach().float().cpu()
-        self.out_conv = _Lin(self._w16(pack_conv3x3(wpad)), self._f32(bpad))
-        self.n_out = oc.weight.shape[0]
+        self.out_conv = self._conv_out_padded(model.out[2])
+        self.n_out = model.out[2].weight.shape[0]
         self._pack_tokenizer(model.position_net)
 
     def repack_first_conv(self, conv):
@@ -489,18 +419,6 @@ class UNetEngine:
             if type(m) == GatedSelfAttentionDense:
                 self.set_fuser_scale(m.scale)
                 return
-
-    # =================================================================================================
-    # buffers
-    # =================================================================================================
-    def buf(self, role: str, shape, dtype=None, zero=False) -> torch.Tensor:
-        dtype = dtype or self.dtype
-        key = (role, tuple(int(s) for s in shape), dtype)
-        t = self._bufs.get(key)
-        if t is None:
-            t = (self.ops.zeros if zero else self.ops.empty)(key[1], dtype)
-            self._bufs[key] = t
-        return t
 
     # =================================================================================================
     # conditioning (step-invariant): UniFusion tokens + per-layer K/V caches
@@ -870,8 +788,7 @@ class UNetEngine:
             slot = cond.clone()
             self._slots[B] = slot
             self._slot_bound[B] = cond.uid
-            for k in [k for k in self._graphs if k[0] == B]:
-                del self._graphs[k]
+            self._drop_graphs(B)
         elif self._slot_bound[B] != cond.uid:
             slot.copy_from(cond)
             self._slot_bound[B] = cond.uid
@@ -889,8 +806,7 @@ class UNetEngine:
                 a.shape[1:] != b.shape[1:] for a, b in zip(slot._tensors(), bank._tensors())) or slot.n_ctx != bank.n_ctx:
             slot = bank.select(idx)
             self._slots[B] = slot
-            for k in [k for k in self._graphs if k[0] == B]:
-                del self._graphs[k]
+            self._drop_graphs(B)
         else:
             for dst, src in zip(slot._tensors(), bank._tensors()):
                 torch.index_select(src, 0, idx, out=dst)
@@ -930,20 +846,9 @@ class UNetEngine:
         else:
             x_s.copy_(x)
             t_s.copy_(t)
-        if not self.use_graphs:
-            self._forward_ops(x_s, t_s, cond, eps_s, fuser_on, paired)
-        else:
-            slot = self._bind(cond)
-            graph = self._graphs.get(key)
-            if graph is None:
-                # eager warm-up sizes every buffer, then capture the identical launch sequence
-                self._forward_ops(x_s, t_s, slot, eps_s, fuser_on, paired)
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with capture_graph(graph):
-                    self._forward_ops(x_s, t_s, slot, eps_s, fuser_on, paired)
-                self._graphs[key] = graph
-            graph.replay()
+        # graphs read the conditioning from the static slot; binding it may drop this batch size's graphs, so it comes first
+        src = self._bind(cond) if self.use_graphs else cond
+        self._replay(key, lambda: self._forward_ops(x_s, t_s, src, eps_s, fuser_on, paired))
         if out is None:
             return eps_s.clone()
         out.copy_(eps_s)

@@ -21,42 +21,20 @@ that (tools/vae_bench.py --encode computes it from the packed layer shapes).
 """
 from __future__ import annotations
 
-from typing import Dict
-
 import torch
 
-from .engine import _Lin, capture_graph, pack_conv3x3
+from .engine_base import EngineBase
 
 
-class _VAEEngine:
-    """What the decoder and the encoder share: weight packing, static buffers, the res / attention blocks, graph capture."""
+class _VAEEngine(EngineBase):
+    """What the decoder and the encoder share on top of ``EngineBase`` (packing primitives, static buffers, graph replay): the
+    packing of the res / attention blocks and the blocks themselves."""
 
     def __init__(self, vae, ops=None, dtype: torch.dtype = torch.bfloat16, use_graphs: bool = True):
-        if ops is None:
-            from .ops import HipOps          # raises when libidf_gfx950.so / the GPU is missing: no fallback
-            ops = HipOps(dtype)
-        self.ops = ops
-        self.dtype = ops.dtype
-        self.device = ops.device
-        self.use_graphs = use_graphs and self.device.type == "cuda"
-        self._bufs: Dict[tuple, torch.Tensor] = {}
-        self._graphs: Dict[tuple, object] = {}
+        super().__init__(ops, dtype, use_graphs)
         self._pack(vae)
 
     # ---- weight packing ---------------------------------------------------------------------------------------
-    def _w16(self, t):
-        return t.detach().to(device=self.device, dtype=torch.float32).to(self.dtype).contiguous()
-
-    def _f32(self, t):
-        return t.detach().to(device=self.device, dtype=torch.float32).contiguous()
-
-    def _conv(self, m) -> _Lin:
-        return _Lin(self._w16(pack_conv3x3(m.weight.detach().float())), self._f32(m.bias))
-
-    def _lin(self, m) -> _Lin:
-        w = m.weight.detach()
-        return _Lin(self._w16(w.reshape(w.shape[0], w.shape[1])), self._f32(m.bias))
-
     def _pack_res(self, rb):
         return dict(cin=rb.in_channels, cout=rb.out_channels,
                     n1=(self._f32(rb.norm1.weight), self._f32(rb.norm1.bias)), conv1=self._conv(rb.conv1),
@@ -72,26 +50,8 @@ class _VAEEngine:
                     wv=self._w16(ab.v.weight.detach().reshape(C, C)), bv=self._f32(ab.v.bias),
                     proj=self._lin(ab.proj_out))
 
-    def _pack_out(self, oc) -> _Lin:
-        """conv_out with few output channels: weights zero-padded to 64 rows (one N tile), the epilogue stores ``n_valid`` of them."""
-        wpad = torch.zeros(64, oc.weight.shape[1], 3, 3)
-        wpad[: oc.weight.shape[0]] = oc.weight.detach().float().cpu()
-        bpad = torch.zeros(64)
-        bpad[: oc.bias.shape[0]] = oc.bias.detach().float().cpu()
-        return _Lin(self._w16(pack_conv3x3(wpad)), self._f32(bpad))
-
     def _pack(self, vae):
         raise NotImplementedError
-
-    # ---- buffers ----------------------------------------------------------------------------------------------
-    def buf(self, role: str, shape, dtype=None) -> torch.Tensor:
-        dtype = dtype or self.dtype
-        key = (role, tuple(int(s) for s in shape), dtype)
-        t = self._bufs.get(key)
-        if t is None:
-            t = self.ops.empty(key[1], dtype)
-            self._bufs[key] = t
-        return t
 
     # ---- blocks -----------------------------------------------------------------------------------------------
     def _res(self, p, x, out_role):
@@ -143,21 +103,6 @@ class _VAEEngine:
                 cur = nxt
         return h
 
-    def _replay(self, key, enqueue):
-        """Run ``enqueue()`` -- a fixed launch sequence over static buffers -- eagerly, or as the hipGraph captured for ``key``."""
-        if not self.use_graphs:
-            enqueue()
-            return
-        graph = self._graphs.get(key)
-        if graph is None:
-            enqueue()                                  # eager warm-up sizes every buffer
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with capture_graph(graph):
-                enqueue()
-            self._graphs[key] = graph
-        graph.replay()
-
 
 class VAEDecoderEngine(_VAEEngine):
     def _pack(self, vae):
@@ -182,7 +127,7 @@ class VAEDecoderEngine(_VAEEngine):
                 layers.append(("up", self._conv(up.upsample.conv)))
             self.levels.append(layers)
         self.norm_out = (self._f32(dec.norm_out.weight), self._f32(dec.norm_out.bias))
-        self.conv_out = self._pack_out(dec.conv_out)
+        self.conv_out = self._conv_out_padded(dec.conv_out)
         self.n_out = dec.conv_out.weight.shape[0]
         self.up_factor = 2 ** (dec.num_resolutions - 1)
 
@@ -233,7 +178,7 @@ class VAEEncoderEngine(_VAEEngine):
         self.mid = [("res", self._pack_res(enc.mid.block_1)), ("attn", self._pack_attn(enc.mid.attn_1)),
                     ("res", self._pack_res(enc.mid.block_2))]
         self.norm_out = (self._f32(enc.norm_out.weight), self._f32(enc.norm_out.bias))
-        self.conv_out = self._pack_out(enc.conv_out)
+        self.conv_out = self._conv_out_padded(enc.conv_out)
         self.n_out = enc.conv_out.weight.shape[0]                       # 2 * z_channels
         self.down_factor = 2 ** (enc.num_resolutions - 1)
 

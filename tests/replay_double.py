@@ -1,6 +1,6 @@
-"""A recording stand-in for ``torch.cuda.CUDAGraph`` + ``engine.capture_graph`` -- TEST DOUBLE ONLY, installed per test with
-``monkeypatch`` -- so that the engines' replay state machine (``_bind``, ``_graphs``, ``_bufs``, ``_replay``) runs on a machine
-without a GPU.
+"""A recording stand-in for ``torch.cuda.CUDAGraph`` + ``engine_base.capture_graph`` -- TEST DOUBLE ONLY, installed per test with
+``monkeypatch`` -- so that the engines' replay state machine (``_bind``, ``_graphs``, ``_bufs``, ``EngineBase._replay``) runs on a
+machine without a GPU.  ``_replay`` is the one place that captures, so ``engine_base`` is the one module patched.
 
 What a hipGraph is for this purpose: a fixed launch list over fixed storage.  While "capturing", every ``EmulOps`` method the
 engine calls is recorded with its argument tensors BY REFERENCE (the ops still execute), and so is every in-place torch call the
@@ -107,8 +107,8 @@ class RecordingOps:
 
 
 def install(monkeypatch) -> Tape:
-    """Route graph construction, capture and ``torch.cuda.synchronize`` of the engine modules to the double."""
-    from instancediffusion_amd import engine as engine_mod, vae_engine as vae_mod
+    """Route graph construction, capture and ``torch.cuda.synchronize`` of ``EngineBase._replay`` to the double."""
+    from instancediffusion_amd import engine_base
     tape = Tape()
 
     @contextlib.contextmanager
@@ -126,8 +126,7 @@ def install(monkeypatch) -> Tape:
     def synchronize(*a, **k):
         tape.syncs += 1
 
-    monkeypatch.setattr(engine_mod, "capture_graph", capture_graph)
-    monkeypatch.setattr(vae_mod, "capture_graph", capture_graph)
+    monkeypatch.setattr(engine_base, "capture_graph", capture_graph)
     monkeypatch.setattr(torch.cuda, "CUDAGraph", lambda: FakeGraph(tape))
     monkeypatch.setattr(torch.cuda, "synchronize", synchronize)
     return tape
@@ -135,9 +134,9 @@ def install(monkeypatch) -> Tape:
 
 def count_real_graphs(monkeypatch) -> Tape:
     """On the GPU: the real capture and replay, counted (``Tape.counts()``)."""
-    from instancediffusion_amd import engine as engine_mod, vae_engine as vae_mod
+    from instancediffusion_amd import engine_base
     tape = Tape()
-    real_capture, real_replay = engine_mod.capture_graph, torch.cuda.CUDAGraph.replay
+    real_capture, real_replay = engine_base.capture_graph, torch.cuda.CUDAGraph.replay
 
     @contextlib.contextmanager
     def capture_graph(graph):
@@ -149,7 +148,6 @@ def count_real_graphs(monkeypatch) -> Tape:
         tape.replays += 1
         return real_replay(self)
 
-    monkeypatch.setattr(engine_mod, "capture_graph", capture_graph)
-    monkeypatch.setattr(vae_mod, "capture_graph", capture_graph)
+    monkeypatch.setattr(engine_base, "capture_graph", capture_graph)
     monkeypatch.setattr(torch.cuda.CUDAGraph, "replay", replay)
     return tape

@@ -6,12 +6,18 @@ over fixed storage).  Per call the oracle is a FRESH engine with graphs off give
 Three deliberately wrong engines (in the spirit of the ``mut`` kernels of tests/attention_cases.py) show that the scripts see the
 failures they are for; the real engine passes all of them.
 """
+import os
+import subprocess
+import sys
+
 import pytest
 import torch
 
 from instancediffusion_amd.engine import UNetEngine
 from tests import replay_cases as rc, replay_double
 from tests.test_replay_cases import eager_engine
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def graph_engine(kind, tape, cls=None):
@@ -51,7 +57,7 @@ def test_stale_slot_handle_raises(monkeypatch):
 
 
 def test_the_double_refuses_an_empty_capture_and_an_allocation_in_a_capture(monkeypatch):
-    from instancediffusion_amd import engine as engine_mod
+    from instancediffusion_amd import engine_base as engine_mod      # where ``install`` patches capture_graph
     from tests.emul_ops import EmulOps
     tape = replay_double.install(monkeypatch)
     ops = replay_double.RecordingOps(EmulOps(torch.float32), tape)
@@ -75,6 +81,17 @@ def test_the_double_refuses_an_empty_capture_and_an_allocation_in_a_capture(monk
     assert bool((b == 5).all()) and tape.counts() == (4, 1)
     with pytest.raises(AssertionError, match="recorded no launch"):
         torch.cuda.CUDAGraph().replay()
+
+
+def test_clip_and_vae_engines_load_without_the_unet_engine():
+    """The shared base lives in ``engine_base``: a fresh interpreter imports the CLIP and VAE engines without ``engine`` (and its
+    ``host.unet``), so not even a value of ``IDF_LN_SELF`` that ``engine`` refuses at import reaches them."""
+    code = ("import sys, instancediffusion_amd.clip_engine, instancediffusion_amd.vae_engine; "
+            "bad = [m for m in ('instancediffusion_amd.engine', 'instancediffusion_amd.host.unet') if m in sys.modules]; "
+            "print('loaded:', bad); sys.exit(1 if bad else 0)")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=REPO,
+                       env=dict(os.environ, IDF_LN_SELF="7", HIP_VISIBLE_DEVICES="-1"))
+    assert r.returncode == 0 and "loaded: []" in r.stdout, r.stdout + r.stderr
 
 
 # ---- deliberately wrong engines ---------------------------------------------------------------------------------------------------
