@@ -14,6 +14,7 @@ MI355X-first design decisions (vs the reference's PyTorch module tree):
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -24,17 +25,6 @@ from .host.attention import SpatialTransformer
 from .host.unet import Downsample, ResBlock, UNetModel, Upsample
 
 
-# LayerNorm statistics of the folded GEMMs (A/B switch, env IDF_LN_SELF): 0 = every producer of the residual stream emits them
-# (out_stats pass), 2 = every LN_ROW consumer sums its own A rows, 1 (default) = q/k and cross-q sum their own, the GEGLU GEMMs
-# take them from the producer.
-LN_SELF_MODE = int(os.environ.get("IDF_LN_SELF", "1"))
-if LN_SELF_MODE not in (0, 1, 2):          # any other value would leave LN_ROW consumers reading statistics nobody wrote
-    raise ValueError(f"IDF_LN_SELF={LN_SELF_MODE}: must be 0, 1 or 2")
-# Round 6: the fused q | k | v projection of the C = 320 level runs on the row-resident kernel (csrc/qkv_fused.hip), which takes
-# the LayerNorm statistics from the caller: there the producers of the self-attention / gated self-attention input (proj_in,
-# attn1's out-projection: plain GEMMs, whose epilogue partials make the statistics almost free) emit them even in mode 1, while
-# the cross-attention query -- fed by the fused feed-forward kernel, which cannot emit them -- keeps summing its own.
-QKV_ROW = os.environ.get("IDF_QKV_ROW", "1") != "0"
 OBJ_TOKENS = 184
 MASK_RES = 64                  # the reference applies the fuser mask only when H*W == 64*64 (attention.py:195)
 
@@ -43,46 +33,77 @@ def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
-# GEGLU weight-row interleave period (A/B switch, env IDF_GEGLU_PERIOD): 64 = [32 value | 32 gate] (value and gate of an output in
-# the two MFMA fragments of a pair: even fragment count per wave, 256-wide tiles), 32 = [16 value | 16 gate] (both in ONE
-# fragment: the GEGLU GEMMs run on the 320-wide persistent tiles -- 9 LDS-DMA instructions per 40 MFMAs instead of 8 per 32,
-# and 20 % fewer tiles re-reading the activation rows).
-GEGLU_PERIOD = int(os.environ.get("IDF_GEGLU_PERIOD", "32"))
-if GEGLU_PERIOD not in (32, 64):
-    raise ValueError(f"IDF_GEGLU_PERIOD={GEGLU_PERIOD}: must be 32 or 64")
-# Fused GEGLU feed-forward (idf_mlp_geglu: one launch per MLP, the 4C-wide intermediate never reaches HBM) where the kernel
-# exists -- the C = 320 blocks -- and the statistics of its LayerNorm are at hand; IDF_MLP_FUSED=0: the two idf_gemm calls
-# (A/B switch; results equal up to the fp32 summation order of the second product).
-MLP_FUSED = os.environ.get("IDF_MLP_FUSED", "1")
-if MLP_FUSED not in ("0", "1"):
-    raise ValueError(f"IDF_MLP_FUSED={MLP_FUSED}: must be 0 or 1")
-MLP_FUSED = MLP_FUSED == "1" and GEGLU_PERIOD == 32
-# ... and only from IDF_MLP_MIN_M token rows up: the kernel's 128-row tiles run one per workgroup slot for ~110-175 us whatever
-# their number, so below a few hundred tiles (a 2-row forward has 64) the two small GEMMs are faster
-# (profiles/r04_mlp_small_m.log).
-MLP_MIN_M = int(os.environ.get("IDF_MLP_MIN_M", "32768"))
-# Paired forwards (classifier-free guidance: rows [n, 2n) carry the SAME latent and timestep as rows [0, n) and differ only in
-# their conditioning): everything in front of the first block that reads the conditioning -- first conv, first ResBlock,
-# GroupNorm, proj_in and the first 64 x 64 self-attention with its out-projection -- is computed ONCE for the n distinct
-# rows and duplicated (exact: those layers see only (x, t)).  IDF_PAIR_HOIST=0 computes all 2n rows (A/B switch).
-PAIR_HOIST = os.environ.get("IDF_PAIR_HOIST", "1")
-if PAIR_HOIST not in ("0", "1"):
-    raise ValueError(f"IDF_PAIR_HOIST={PAIR_HOIST}: must be 0 or 1")
-PAIR_HOIST = PAIR_HOIST == "1"
-# Round 5: every 3x3 conv whose output feeds a GroupNorm leaves that GroupNorm's partial statistics from its epilogue registers
-# (idf_conv3x3 gn_partial), and the GroupNorm runs its normalise pass only.  IDF_GN_EPI=0: every GroupNorm runs both passes.
-GN_EPI = os.environ.get("IDF_GN_EPI", "1")
-if GN_EPI not in ("0", "1"):
-    raise ValueError(f"IDF_GN_EPI={GN_EPI}: must be 0 or 1")
-GN_EPI = GN_EPI == "1"
-# The three Upsample layers (nearest x2, then a 3x3 conv) run as four 2x2 phase convs on the low-resolution image, the upsample
-# folded into the weights at pack time (pack_conv_up2x, idf_conv_up2x_folded): 4 Cin multiply-adds per output pixel instead of 9 Cin.
-# IDF_UP_FOLD=0: the 3x3 conv with the upsample in its gather (idf_conv3x3 upsample=1), as before.
-UP_FOLD = os.environ.get("IDF_UP_FOLD", "1")
-if UP_FOLD not in ("0", "1"):
-    raise ValueError(f"IDF_UP_FOLD={UP_FOLD}: must be 0 or 1")
-UP_FOLD = UP_FOLD == "1"
-DEBUG_PAIRED = os.environ.get("IDF_DEBUG_PAIRED", "0") == "1"     # verify the paired=True guarantee on EVERY forward_cond call
+@dataclasses.dataclass(frozen=True)
+class EngineKnobs:
+    """The engine's host-side A/B switches as one validated value (``UNetEngine.knobs``).  ``from_env()`` reads the environment when an
+    engine is CONSTRUCTED, not when this module is imported; a test passes ``dataclasses.replace(EngineKnobs.from_env(), ..)``."""
+    # LayerNorm statistics of the folded GEMMs: 0 = every producer of the residual stream emits them (out_stats pass), 2 = every
+    # LN_ROW consumer sums its own A rows, 1 = q/k and cross-q sum their own, the GEGLU GEMMs take them from the producer.  Who
+    # reads what in which mode: ``UNetEngine._ln_routing``.
+    ln_self: int = 1
+    # The fused q | k | v projection of the C = 320 level runs on the row-resident kernel (csrc/qkv_fused.hip), which takes the
+    # statistics from the caller: the producers in front of it (proj_in, attn1's out-projection: plain GEMMs, whose epilogue
+    # partials make the statistics almost free) emit them even in mode 1.
+    qkv_row: bool = True
+    # GEGLU weight-row interleave period: 64 = [32 value | 32 gate] (value and gate of an output in the two MFMA fragments of a
+    # pair: even fragment count per wave, 256-wide tiles), 32 = [16 value | 16 gate] (both in ONE fragment: the GEGLU GEMMs run on
+    # the 320-wide persistent tiles -- 9 LDS-DMA instructions per 40 MFMAs instead of 8 per 32, and 20 % fewer tiles re-reading
+    # the activation rows).
+    geglu_period: int = 32
+    # Fused GEGLU feed-forward (idf_mlp_geglu: one launch per MLP, the 4C-wide intermediate never reaches HBM) where the kernel
+    # exists -- the C = 320 blocks -- and the statistics of its LayerNorm are at hand; off: the two idf_gemm calls (results equal
+    # up to the fp32 summation order of the second product).  Needs the period-32 packing: from_env() turns it off with period 64.
+    mlp_fused: bool = True
+    # ... and only from this many token rows up: the kernel's 128-row tiles run one per workgroup slot for ~110-175 us whatever
+    # their number, so below a few hundred tiles (a 2-row forward has 64) the two small GEMMs are faster
+    # (profiles/r04_mlp_small_m.log).
+    mlp_min_m: int = 32768
+    # Paired forwards (classifier-free guidance: rows [n, 2n) carry the SAME latent and timestep as rows [0, n) and differ only in
+    # their conditioning): everything in front of the first block that reads the conditioning -- first conv, first ResBlock,
+    # GroupNorm, proj_in and the first 64 x 64 self-attention with its out-projection -- is computed ONCE for the n distinct
+    # rows and duplicated (exact: those layers see only (x, t)).  Off: all 2n rows are computed.
+    pair_hoist: bool = True
+    # Every 3x3 conv whose output feeds a GroupNorm leaves that GroupNorm's partial statistics from its epilogue registers
+    # (idf_conv3x3 gn_partial), and the GroupNorm runs its normalise pass only.  Off: every GroupNorm runs both passes.
+    gn_epi: bool = True
+    # The three Upsample layers (nearest x2, then a 3x3 conv) run as four 2x2 phase convs on the low-resolution image, the upsample
+    # folded into the weights at pack time (pack_conv_up2x, idf_conv_up2x_folded): 4 Cin multiply-adds per output pixel instead of
+    # 9 Cin.  Off: the 3x3 conv with the upsample in its gather (idf_conv3x3 upsample=1).
+    up_fold: bool = True
+    # The fused q | k | v launch (see _self_attn), from vt_min_n tokens per sample.  256 (was 1024): at the 16 x 16 level the fused
+    # launch (M32768 N3840 K1280, y read once) replaces the q | k GEMM + the batched 62-%-padded V^T GEMM (2.05 ms per 128-row
+    # forward at 523 TF): 165.9 -> 164.7 ms per forward on one box, 64 no further gain (profiles/r05_vt_min_n_ab.log)
+    vt_global: bool = True
+    vt_min_n: int = 256
+    debug_paired: bool = False     # verify the paired=True guarantee on EVERY forward_cond call
+
+    # field, environment name, default, parser of the raw string (``bool``: strictly "0" or "1")
+    _ENV = (("ln_self", "IDF_LN_SELF", "1", int), ("qkv_row", "IDF_QKV_ROW", "1", lambda s: s != "0"), ("geglu_period", "IDF_GEGLU_PERIOD", "32", int),
+            ("mlp_fused", "IDF_MLP_FUSED", "1", bool), ("mlp_min_m", "IDF_MLP_MIN_M", "32768", int), ("pair_hoist", "IDF_PAIR_HOIST", "1", bool),
+            ("gn_epi", "IDF_GN_EPI", "1", bool), ("up_fold", "IDF_UP_FOLD", "1", bool), ("vt_global", "IDF_VT_GLOBAL", "1", lambda s: s != "0"),
+            ("vt_min_n", "IDF_VT_MIN_N", "256", int), ("debug_paired", "IDF_DEBUG_PAIRED", "0", lambda s: s == "1"))
+
+    def __post_init__(self):
+        if self.ln_self not in (0, 1, 2):      # any other value would leave LN_ROW consumers reading statistics nobody wrote
+            raise ValueError(f"IDF_LN_SELF={self.ln_self}: must be 0, 1 or 2")
+        if self.geglu_period not in (32, 64):
+            raise ValueError(f"IDF_GEGLU_PERIOD={self.geglu_period}: must be 32 or 64")
+        if self.mlp_fused and self.geglu_period != 32:
+            raise ValueError("mlp_fused needs geglu_period 32 (the fused kernel's operand images are packed from it)")
+        if self.vt_min_n < 64 or self.vt_min_n % 64:
+            raise ValueError(f"IDF_VT_MIN_N={self.vt_min_n}: a positive multiple of 64 (tokens per sample from which the fused "
+                             "q | k | v launch is used; default 256)")
+
+    @classmethod
+    def from_env(cls) -> "EngineKnobs":
+        v = {}
+        for field, env, default, parse in cls._ENV:
+            raw = os.environ.get(env, default)
+            if parse is bool and raw not in ("0", "1"):
+                raise ValueError(f"{env}={raw}: must be 0 or 1")
+            v[field] = raw == "1" if parse is bool else parse(raw)
+        v["mlp_fused"] = v["mlp_fused"] and v["geglu_period"] == 32
+        return cls(**v)
 
 
 def pack_geglu(w: torch.Tensor, b: torch.Tensor, period: int = 64) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -176,19 +197,13 @@ class Cond:
 
 
 class UNetEngine(EngineBase):
-    def __init__(self, model: UNetModel, ops=None, dtype: torch.dtype = torch.bfloat16, use_graphs: bool = True):
+    def __init__(self, model: UNetModel, ops=None, dtype: torch.dtype = torch.bfloat16, use_graphs: bool = True,
+                 knobs: Optional[EngineKnobs] = None):
         super().__init__(ops, dtype, use_graphs)
         self.model = model
         self.heads = model.num_heads
         self.masked_fuser = not getattr(model, "efficient_attention", True)     # attention.py:189
-        self.vt_global = os.environ.get("IDF_VT_GLOBAL", "1") != "0"            # A/B knob, see _self_attn
-        # fewest tokens per sample for the fused q | k | v launch.  Round 5: 256 (was 1024) -- at the 16 x 16 level the fused launch
-        # (M32768 N3840 K1280, y read once) replaces the q | k GEMM + the batched 62-%-padded V^T GEMM (2.05 ms per 128-row forward
-        # at 523 TF): 165.9 -> 164.7 ms per forward on one box, 64 no further gain (profiles/r05_vt_min_n_ab.log)
-        self.vt_min_n = int(os.environ.get("IDF_VT_MIN_N", "256"))
-        if self.vt_min_n < 64 or self.vt_min_n % 64:
-            raise ValueError(f"IDF_VT_MIN_N={self.vt_min_n}: a positive multiple of 64 (tokens per sample from which the fused "
-                             "q | k | v launch is used; default 256)")
+        self.knobs = knobs or EngineKnobs.from_env()
         self._paired_checked: set = set()
         self._cond_cache: Dict[tuple, Cond] = {}
         self._slots: Dict[int, Cond] = {}                      # batch size -> static Cond the hipGraphs read from
@@ -203,7 +218,7 @@ class UNetEngine(EngineBase):
     def _pack_up(self, m) -> dict:
         """Upsample conv: the four folded 2x2 phase images (pack_conv_up2x) when the folded path is active, and then NOT the 3x3
         image -- ``_up_conv3`` packs that one on demand, for a forward whose shape the folded launch does not take."""
-        if UP_FOLD and hasattr(self.ops, "conv_up2x"):
+        if self.knobs.up_fold and hasattr(self.ops, "conv_up2x"):
             return dict(kind="up", conv=None, fold=self._w16(pack_conv_up2x(m.weight.detach().float())), b=self._f32(m.bias), mod=m)
         return dict(kind="up", conv=self._conv(m), fold=None)
 
@@ -213,14 +228,14 @@ class UNetEngine(EngineBase):
         return p["conv"]
 
     def _pack_ff(self, ff, norm):
-        """GEGLU feed-forward behind LayerNorm `norm`: proj rows interleaved value | gate per GEGLU_PERIOD (pack_geglu), gamma folded."""
+        """GEGLU feed-forward behind LayerNorm `norm`: proj rows interleaved value | gate per ``knobs.geglu_period`` (pack_geglu), gamma folded."""
         w = ff.net[0].proj.weight.detach().float()
         g, b = norm.weight.detach().float(), norm.bias.detach().float()
-        wp, dp = pack_geglu(w * g[None, :], ff.net[0].proj.bias.detach().float() + w @ b, GEGLU_PERIOD)
+        wp, dp = pack_geglu(w * g[None, :], ff.net[0].proj.bias.detach().float() + w @ b, self.knobs.geglu_period)
         w16 = self._w16(wp)
         f = dict(w1=w16, b1=self._f32(dp), c1=w16.float().sum(1).contiguous(), l2=self._lin(ff.net[2]))
         C = w.shape[1]
-        if MLP_FUSED and hasattr(self.ops, "mlp_geglu") and self.ops.mlp_supported(128, C):
+        if self.knobs.mlp_fused and hasattr(self.ops, "mlp_geglu") and self.ops.mlp_supported(128, C):
             f["cd"], f["w2p"] = self.ops.mlp_pack(w16, f["c1"], f["b1"], f["l2"].w)
         return f
 
@@ -539,7 +554,7 @@ class UNetEngine(EngineBase):
     # =================================================================================================
     def _gnp(self, role, B, HW, C):
         """Buffer for the GroupNorm partial statistics a conv3x3 leaves for the GroupNorm that reads its output, or None."""
-        shape = self.ops.gn_partial_shape(B, HW, C) if (GN_EPI and hasattr(self.ops, "gn_partial_shape")) else None
+        shape = self.ops.gn_partial_shape(B, HW, C) if (self.knobs.gn_epi and hasattr(self.ops, "gn_partial_shape")) else None
         return None if shape is None else self.buf(role, shape, torch.float32)
 
     def _res(self, p, x, emb_all, out_role, gnp=None, want_out=True):
@@ -562,81 +577,88 @@ class UNetEngine(EngineBase):
         p2 = self._gnp("gnp.out", B, H * W, Cout) if want_out else None
         return ops.conv3x3(g2, p["conv2"].w, self.buf(out_role, (B, H, W, Cout)), bias=p["conv2"].b, res=xs, gn_partial=p2), p2
 
-    def _self_attn(self, a, y, st, B, N, C, kv_extra=None, vis=None):
+    def _self_attn(self, a, y, st, handed, B, N, C, kv_extra=None, vis=None):
         """y [B*N, C] residual stream (raw), st [B*N, 2] its LayerNorm statistics (mu, rstd); the LayerNorm itself is folded
-        into the projections (``_fold_ln``).  Returns the attention output [B, N, C] (pre out-proj).
+        into the projections (``_fold_ln``).  ``handed`` (``_ln_routing``): the GEMM that wrote y left the statistics in st;
+        otherwise the q | k (| v) projection sums them in its own K loop and leaves them in st.  Returns the attention output
+        [B, N, C] (pre out-proj).  ``kv_extra``: (k, vt) of the grounding tokens, the second KV segment of the gated self-attention;
         ``vis``: (qbits, kbits0, kbits1) visibility words of the masked gated self-attention, or None."""
         ops = self.ops
-        fused = self.vt_global and N % 64 == 0 and N >= self.vt_min_n
-        if fused:
+        if self._qkv_fused(N):
             # fused q | k | v projection (round 3): ONE GEMM over the [3C, C] image reads y once; its last C columns are
             # stored TRANSPOSED straight into the batch-interleaved V^T image [C][B][N] (the attention kernel reads sample b
             # through base + b*N, ld = B*N), replacing the second GEMM V^T = Wv . y^T (M = C: 62 % tile padding at C = 320)
-            # that re-read y.  The LayerNorm statistics come from the K loop itself where that is free (C = 320), else `st`.
+            # that re-read y.
             vtg = self.buf("st.vtg", (C, B * N))
-            own = self._qkv_self(C, N)
-            qk = ops.gemm(y, a["wqkv"], self.buf("st.qk", (B * N, 2 * C)), bias=a["dqkv"],
-                          ln_row=(None if own else st, a["cqkv"]), ln_stats_out=st if own else None,
-                          vt_out=vtg).view(B, N, 2 * C)
+            qk = ops.gemm(y, a["wqkv"], self.buf("st.qk", (B * N, 2 * C)), bias=a["dqkv"], ln_row=(st if handed else None, a["cqkv"]),
+                          ln_stats_out=None if handed else st, vt_out=vtg).view(B, N, 2 * C)
             vt = vtg.view(C, B, N).permute(1, 0, 2)
         else:
-            # the q/k projection computes the LayerNorm statistics of y's rows in its own K loop and leaves them in st for
-            # the transposed-V projection below
-            if self._ln_self(C):
-                qk = ops.gemm(y, a["wqk"], self.buf("st.qk", (B * N, 2 * C)), bias=a["dqk"], ln_row=(None, a["cqk"]),
-                              ln_stats_out=st).view(B, N, 2 * C)
-            else:
-                qk = ops.gemm(y, a["wqk"], self.buf("st.qk", (B * N, 2 * C)), bias=a["dqk"], ln_row=(st, a["cqk"])).view(B, N, 2 * C)
+            # the transposed-V projection reads the statistics from st either way
+            qk = ops.gemm(y, a["wqk"], self.buf("st.qk", (B * N, 2 * C)), bias=a["dqk"], ln_row=(st if handed else None, a["cqk"]),
+                          ln_stats_out=None if handed else st).view(B, N, 2 * C)
             ldv = _round_up(N, 64)
             vt = self.buf("st.vt", (B, C, ldv), zero=True)
             ops.gemm(a["wv"], y.view(B, N, C), vt[:, :, :N], ln_col=(st.view(B, N, 2), a["cv"], a["dv"]))
         att = self.buf("st.att", (B, N, C))
-        if kv_extra is None:
-            ops.attention(qk[:, :, :C], qk[:, :, C:], vt, N, att, self.heads)
-        elif vis is None:
-            ops.attention(qk[:, :, :C], qk[:, :, C:], vt, N, att, self.heads, k1=kv_extra[0], vt1=kv_extra[1],
-                          n1=OBJ_TOKENS)
-        else:
-            ops.attention(qk[:, :, :C], qk[:, :, C:], vt, N, att, self.heads, k1=kv_extra[0], vt1=kv_extra[1],
-                          n1=OBJ_TOKENS, qbits=vis[0], kbits0=vis[1], kbits1=vis[2])
+        k1, vt1 = kv_extra or (None, None)
+        qbits, kbits0, kbits1 = vis or (None, None, None)
+        ops.attention(qk[:, :, :C], qk[:, :, C:], vt, N, att, self.heads, k1=k1, vt1=vt1, n1=OBJ_TOKENS if kv_extra else 0,
+                      qbits=qbits, kbits0=kbits0, kbits1=kbits1)
         return att
 
-    def _qkv_self(self, C, N):
-        """Does the fused q | k | v projection sum its own statistics?  Not where the row-resident kernel takes the launch."""
-        return self._ln_self(C) and not (QKV_ROW and C == 320 and self.vt_global and N % 64 == 0 and N >= self.vt_min_n)
+    def _qkv_fused(self, N):
+        """Does a self-attention over N tokens per sample project q | k | v in ONE launch (V^T in the global layout)?"""
+        return self.knobs.vt_global and N % 64 == 0 and N >= self.knobs.vt_min_n
 
-    @staticmethod
-    def _ln_self(C):
-        """Do the q/k and cross-q projections of a C-channel level sum their own A rows?  Mode 1: only where the projection
-        is HBM-bound (C = 320: the in-loop v_dot2c sums share the matrix pipe and cost 12 % on the MFMA-bound levels, more
-        than the 8-B-per-row statistics pass they replace there)."""
-        return LN_SELF_MODE == 2 or (LN_SELF_MODE == 1 and C <= 320)
-
-    def _ff(self, f, y, st, M, C, gate=None, out_stats=None):
-        """y += [gate *] GEGLU-FF(LN(y)); the LayerNorm is folded into the first GEMM (statistics st, left by the GEMM that
-        produced y: a GEGLU GEMM has 8-16 column tiles per row block, each of which would repeat the in-loop row sums --
-        measured +15 % on those launches -- so here the separate 8-B-per-row pass is the cheaper form)."""
+    def _ff(self, f, y, st, handed, M, C, gate=None, out_stats=None):
+        """y += [gate *] GEGLU-FF(LN(y)); the LayerNorm is folded into the first GEMM.  ``handed`` (``_ln_routing``): its
+        statistics are in st, left by the GEMM that wrote y; only then, and asked for no ``out_stats`` of its own, can the
+        feed-forward run as the one-launch fused MLP."""
         ops = self.ops
-        if out_stats is None and st is not None and self._ff_fused(f, M, C):
+        if handed and out_stats is None and self._ff_fused(f, M, C):
             return ops.mlp_geglu(y, st, f["w1"], f["cd"], f["w2p"], f["l2"].b, y, gate=gate)
-        mid = ops.gemm(y, f["w1"], self.buf("st.ffmid", (M, 4 * C)), bias=f["b1"], geglu=True, geglu_period=GEGLU_PERIOD,
-                       ln_row=(None if LN_SELF_MODE == 2 else st, f["c1"]))
+        mid = ops.gemm(y, f["w1"], self.buf("st.ffmid", (M, 4 * C)), bias=f["b1"], geglu=True, geglu_period=self.knobs.geglu_period,
+                       ln_row=(st if handed else None, f["c1"]))
         return ops.gemm(mid, f["l2"].w, y, bias=f["l2"].b, res=y, gate=gate, out_stats=out_stats)
 
     def _ff_fused(self, f, M, C):
-        """Does a feed-forward that is asked for no output statistics run as the one-launch fused MLP?"""
-        return "w2p" in f and LN_SELF_MODE != 2 and M >= MLP_MIN_M and self.ops.mlp_supported(M, C)
+        """Does a feed-forward that is handed its statistics and asked for none run as the one-launch fused MLP?"""
+        return "w2p" in f and M >= self.knobs.mlp_min_m and self.ops.mlp_supported(M, C)
 
-    def _q_row(self, p, M, C, fuser_on):
-        """Is the cross-attention query of M rows handed its statistics instead of summing them in its K loop?  Where the
-        weights-resident streaming kernel takes that launch (the library's knobs and threshold: ``ops.proj_row_takes``) and
-        its producer emits them from an idf_gemm epilogue: attn1's out-projection (same kernel: final (mu, rstd) for free),
-        or the two-GEMM form of the fuser's feed-forward.  The fused MLP launch has no statistics output, so behind it the
-        query keeps its own sums."""
+    def _ln_routing(self, p, C, N, M, fuser_on):
+        """Who supplies the LayerNorm statistics (mu, rstd) of the residual stream y to each GEMM of one block that reads LN(y):
+        the GEMM that last wrote y (``out_stats``, an 8-B-per-row pass in its epilogue: the reader is HANDED them) or the reader
+        itself, from sums over its own A rows in its K loop.  Readers in block order, with the locals below:
+
+            attn1   q | k | v  norm1          handed iff not qkv_self
+            f_attn  q | k | v  fuser.norm1    handed iff not qkv_self        (fuser on only)
+            f_ff    GEGLU      fuser.norm2    handed iff knobs.ln_self <= 1  (fuser on only)
+            attn2   q          norm2          handed iff not q_self
+            ff      GEGLU      norm3          handed iff knobs.ln_self <= 1
+
+        The writers of y in block order are proj_in and then each reader's own sub-block (attn1.out, f_attn.out, f_ff, attn2.out,
+        ff); a writer emits iff the NEXT reader is handed.  M: the block's rows behind the duplication of a paired forward.
+        Returns (handed: reader -> bool, emits: writer -> bool, keyed "proj_in" and by sub-block): ``_st`` feeds a reader and the
+        writer in front of it from the one value, so they cannot disagree.  A new reader of LN(y) is one more line here."""
+        k = self.knobs
+        # do the q/k and cross-q projections of this level sum their own A rows?  Mode 1: only where the projection is HBM-bound
+        # (C = 320: the in-loop v_dot2c sums share the matrix pipe and cost 12 % on the MFMA-bound levels, more than the
+        # 8-B-per-row statistics pass they replace there).  A GEGLU GEMM has 8-16 column tiles per row block, each of which would
+        # repeat the in-loop row sums -- measured +15 % on those launches -- so it sums its own in mode 2 only.
+        ln_self = k.ln_self == 2 or (k.ln_self == 1 and C <= 320)
+        # ... the q | k (| v) projection not where the row-resident kernel takes the fused launch: it wants them handed
+        qkv_self = ln_self and not (k.qkv_row and C == 320 and self._qkv_fused(N))
+        # ... the query not where the weights-resident streaming kernel takes that launch (the library's knobs and threshold:
+        # ``ops.proj_row_takes``) and its producer emits from an idf_gemm epilogue: attn1's out-projection (same kernel: final
+        # (mu, rstd) for free), or the two-GEMM form of the fuser's feed-forward.  The fused MLP launch has no statistics output,
+        # so behind it the query keeps its own sums: f_ff runs fused only when the query behind it is not handed.
         takes = getattr(self.ops, "proj_row_takes", None)
-        if LN_SELF_MODE != 1 or takes is None or not takes(M, C):
-            return False
-        return not (fuser_on and self._ff_fused(p["f_ff"], M, C))
+        q_self = ln_self and not (k.ln_self == 1 and takes is not None and takes(M, C)
+                                  and not (fuser_on and self._ff_fused(p["f_ff"], M, C)))
+        handed = dict(attn1=not qkv_self, **(dict(f_attn=not qkv_self, f_ff=k.ln_self <= 1) if fuser_on else {}),
+                      attn2=not q_self, ff=k.ln_self <= 1)
+        return handed, dict(zip(["proj_in", *handed], [*handed.values(), False]))
 
     def _dup(self, t: torch.Tensor, role: str) -> torch.Tensor:
         """[n, ...] -> [2n, ...]: both halves a copy of t (the second half of a paired forward)."""
@@ -648,57 +670,43 @@ class UNetEngine(EngineBase):
 
     def _st(self, p, x, cond: Cond, fuser_on: bool, dup: bool = False, gnp=None):
         """SpatialTransformer (attention.py:366-379).  No LayerNorm kernel runs: every GEMM that reads LN(y) reads y itself
-        against gamma-folded weights and applies (mu, rstd) in its epilogue.  The q/k and cross-q projections sum their A
-        rows in their own K loop (the q/k one hands the statistics to the transposed-V projection); the GEGLU GEMMs take
-        them from the out-projection that wrote y (``out_stats``: an 8-B-per-row pass inside that idf_gemm call).
-        ``dup``: x holds the n DISTINCT rows of a paired forward (see PAIR_HOIST); the block's input and its residual stream
-        are duplicated to 2n rows behind the self-attention, the last layer that does not read the conditioning."""
+        against gamma-folded weights and applies (mu, rstd) in its epilogue; who computes them is ``_ln_routing``'s table.
+        ``dup``: x holds the n DISTINCT rows of a paired forward (see ``EngineKnobs.pair_hoist``); the block's input and its
+        residual stream are duplicated to 2n rows behind the self-attention, the last layer that does not read the conditioning."""
         ops = self.ops
         B, H, W, C = x.shape
         N, M = H * W, B * H * W
         g = ops.groupnorm(x, self.buf("gn", x.shape), p["norm"][0], p["norm"][1], 1e-6, False, partial=gnp)
-        st = self.buf("st.stats", (M, 2), torch.float32)
-        own = self._ln_self(C) and not self._q_row(p, 2 * M if dup else M, C, fuser_on)
-        own_qkv = self._qkv_self(C, N)
-        # which producers emit statistics: `pqkv` those in front of a q | k | v projection, `pre` the one in front of the
-        # cross-attention query, `ffs` those in front of a feed-forward
-        pre, ffs = (None if own else st), (st if LN_SELF_MODE <= 1 else None)
-        pqkv = None if own_qkv else st
-        y = ops.gemm(g.view(M, C), p["proj_in"].w, self.buf("st.x", (M, C)), bias=p["proj_in"].b, out_stats=pqkv)
+        st = self.buf("st.stats", (M, 2), torch.float32)       # the current statistics buffer: whatever a writer emits goes here
+        handed, emits = self._ln_routing(p, C, N, 2 * M if dup else M, fuser_on)
+        y = ops.gemm(g.view(M, C), p["proj_in"].w, self.buf("st.x", (M, C)), bias=p["proj_in"].b,
+                     out_stats=st if emits["proj_in"] else None)
         # --- self attention (attention.py:334): LN norm1
-        att = self._self_attn(p["attn1"], y, st, B, N, C)
-        ops.gemm(att.view(M, C), p["attn1"]["out"].w, y, bias=p["attn1"]["out"].b, res=y,
-                 out_stats=pqkv if fuser_on else pre)
+        att = self._self_attn(p["attn1"], y, st, handed["attn1"], B, N, C)
+        ops.gemm(att.view(M, C), p["attn1"]["out"].w, y, bias=p["attn1"]["out"].b, res=y, out_stats=st if emits["attn1"] else None)
         if dup:
             x, y = self._dup(x, "st.x_in2"), self._dup(y.view(B, N, C), "st.x2").view(2 * M, C)
-            if (pqkv if fuser_on else pre) is not None:
-                st = self._dup(st.view(B, N, 2), "st.stats2").view(2 * M, 2)
-                pre = st if pre is not None else None
-                pqkv = st if pqkv is not None else None
-                ffs = st if ffs is not None else None
-            else:
-                st = self.buf("st.stats", (2 * M, 2), torch.float32)
-                pre = st if pre is not None else None       # (written by a producer behind this point: f_ff with the fuser on)
-                pqkv = st if pqkv is not None else None
-                ffs = st if ffs is not None else None
+            # what attn1.out emitted is duplicated with its rows; otherwise the writers behind this point get a 2n-row buffer
+            st = (self._dup(st.view(B, N, 2), "st.stats2").view(2 * M, 2) if emits["attn1"]
+                  else self.buf("st.stats", (2 * M, 2), torch.float32))
             B, M = 2 * B, 2 * M
         # --- gated self attention over [visual ; grounding tokens] (attention.py:304-311): LN fuser.norm1 / norm2
         i = p["idx"]
         if fuser_on:
             vis = cond.vis if (cond.vis and N == MASK_RES * MASK_RES) else None
-            att = self._self_attn(p["f_attn"], y, st, B, N, C, kv_extra=(cond.k_obj[i], cond.vt_obj[i]), vis=vis)
+            att = self._self_attn(p["f_attn"], y, st, handed["f_attn"], B, N, C, kv_extra=(cond.k_obj[i], cond.vt_obj[i]), vis=vis)
             ops.gemm(att.view(M, C), p["f_attn"]["out"].w, y, bias=p["f_attn"]["out"].b, res=y, gate=self.gates[i, 0:1],
-                     out_stats=ffs)
-            self._ff(p["f_ff"], y, st, M, C, gate=self.gates[i, 1:2], out_stats=pre)
+                     out_stats=st if emits["f_attn"] else None)
+            self._ff(p["f_ff"], y, st, handed["f_ff"], M, C, gate=self.gates[i, 1:2], out_stats=st if emits["f_ff"] else None)
         # --- cross attention (attention.py:336): LN norm2 on the query side
         a2 = p["attn2"]
         q = ops.gemm(y, a2["wq"], self.buf("st.q", (M, C)), bias=a2["dq"],
-                     ln_row=(None if own else st, a2["cq"])).view(B, N, C)
+                     ln_row=(st if handed["attn2"] else None, a2["cq"])).view(B, N, C)
         att = self.buf("st.att", (B, N, C))
         ops.attention(q, cond.k_ctx[i], cond.vt_ctx[i], cond.n_ctx, att, self.heads)
-        ops.gemm(att.view(M, C), a2["out"].w, y, bias=a2["out"].b, res=y, out_stats=ffs)
+        ops.gemm(att.view(M, C), a2["out"].w, y, bias=a2["out"].b, res=y, out_stats=st if emits["attn2"] else None)
         # --- feed forward (attention.py:337): LN norm3
-        self._ff(p["ff"], y, st, M, C)
+        self._ff(p["ff"], y, st, handed["ff"], M, C)
         # --- proj_out + x_in (attention.py:378-379), in place on the block input
         ops.gemm(y, p["proj_out"].w, x.view(M, C), bias=p["proj_out"].b, res=x.view(M, C))
         return x
@@ -739,11 +747,11 @@ class UNetEngine(EngineBase):
     def _forward_ops(self, x: torch.Tensor, t_f32: torch.Tensor, cond: Cond, eps: torch.Tensor, fuser_on: bool,
                      paired: bool = False):
         """Enqueue one UNet forward (openaimodel.py:482-563).  x [B,4,H,W] fp32, t_f32 [B], eps [B,4,H,W] fp32.
-        ``paired``: rows [B/2, B) repeat the latent and timestep of rows [0, B/2) (see PAIR_HOIST)."""
+        ``paired``: rows [B/2, B) repeat the latent and timestep of rows [0, B/2) (see ``EngineKnobs.pair_hoist``)."""
         ops = self.ops
         B = x.shape[0]
         # the hoist needs the reference layout: input block 0 = first conv, input block 1 = ResBlock + SpatialTransformer
-        hoist = (paired and PAIR_HOIST and B % 2 == 0 and len(self.in_blocks) > 1
+        hoist = (paired and self.knobs.pair_hoist and B % 2 == 0 and len(self.in_blocks) > 1
                  and [p["kind"] for p in self.in_blocks[0]] == ["conv_in"] and [p["kind"] for p in self.in_blocks[1]] == ["res", "st"])
         n = B // 2
         mc = self.model.model_channels
@@ -818,7 +826,7 @@ class UNetEngine(EngineBase):
         """eps = UNet(x, t | cond).  The launch sequence is captured once per (batch, resolution, fuser on/off, paired)
         into a hipGraph over static buffers and replayed; conditioning is copied into a static slot when it changes.
         ``paired``: a [cond | uncond] guidance batch -- rows [B/2, B) carry the latent and timestep of rows [0, B/2), and the
-        conditioning-free prefix of the network runs once (PAIR_HOIST).  Pass the B/2 DISTINCT rows (x: [B/2, ...], t: [B/2]): the
+        conditioning-free prefix of the network runs once (``knobs.pair_hoist``).  Pass the B/2 DISTINCT rows (x: [B/2, ...], t: [B/2]): the
         engine writes both halves of its static input itself, so the invariant holds by construction.  A full
         [B, ...] batch is still accepted; it is then VERIFIED the first time a launch configuration is used (one compare + host
         sync per (B, H, W, fuser, paired) key; on every call with IDF_DEBUG_PAIRED=1), not on later calls."""
@@ -829,7 +837,7 @@ class UNetEngine(EngineBase):
         _, Cx, H, W = x.shape
         fuser_on = self.fuser_scale != 0.0
         key = (B, H, W, fuser_on, bool(paired))
-        if paired and not half and (DEBUG_PAIRED or key not in self._paired_checked):
+        if paired and not half and (self.knobs.debug_paired or key not in self._paired_checked):
             n = B // 2
             if B % 2 or not (torch.equal(x[:n], x[n:]) and torch.equal(t[:n], t[n:])):
                 raise ValueError("forward_cond(paired=True): rows [B/2, B) must repeat the latent and timestep of rows [0, B/2)")

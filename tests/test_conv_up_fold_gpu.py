@@ -7,6 +7,8 @@ with the fp32 MASTER weights (the folded image is summed in fp32 and rounded to 
 max error <= 2^-7 of the output max, rel-RMS <= 3e-3, in bf16 and fp16.  Every case also prints its rel-RMS against today's
 conv3x3(upsample=1) on the same inputs.  Then the engine: IDF_UP_FOLD=0 is bit-identical to the path without the op.
 """
+import dataclasses
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -181,11 +183,10 @@ def test_engine_knob_off_is_the_parent_path_bit_for_bit(lib, forced, monkeypatch
         eps = eng.forward_cond(x.cuda(), t.cuda(), cond).float().cpu()
         return eps, calls
 
-    monkeypatch.setattr(E, "UP_FOLD", False)
-    eng_off = E.UNetEngine(model, ops=HipOps(torch.bfloat16), use_graphs=False)
-    monkeypatch.setattr(E, "UP_FOLD", True)
-    eng_parent = E.UNetEngine(model, ops=_WithoutFold(HipOps(torch.bfloat16)), use_graphs=False)
-    eng_on = E.UNetEngine(model, ops=HipOps(torch.bfloat16), use_graphs=False)
+    on = dataclasses.replace(E.EngineKnobs.from_env(), up_fold=True)
+    eng_off = E.UNetEngine(model, ops=HipOps(torch.bfloat16), use_graphs=False, knobs=dataclasses.replace(on, up_fold=False))
+    eng_parent = E.UNetEngine(model, ops=_WithoutFold(HipOps(torch.bfloat16)), use_graphs=False, knobs=on)
+    eng_on = E.UNetEngine(model, ops=HipOps(torch.bfloat16), use_graphs=False, knobs=on)
     ups = [m for m in model.modules() if type(m).__name__ == "Upsample"]
     assert len(_up_layers(eng_off)) == len(ups) == 2
     for eng in (eng_off, eng_parent):

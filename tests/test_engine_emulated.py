@@ -3,13 +3,14 @@ caches and two-segment attention bookkeeping are exercised against the CPU oracl
 CPU op emulation in tests/emul_ops.py.  With fp32 storage the engine must agree with the reference to fp32 round-off;
 with bf16 storage the error shows what to expect from the MI355X kernels.
 """
+import dataclasses
 import os
 
 import pytest
 import torch
 
 from instancediffusion_amd import synth
-from instancediffusion_amd.engine import UNetEngine, pack_geglu
+from instancediffusion_amd.engine import EngineKnobs, UNetEngine, pack_geglu
 from instancediffusion_amd.host.config import unet_kwargs_from_cfg
 from ldm.modules.diffusionmodules.openaimodel import UNetModel
 from grounding_input.text_grounding_tokinzer_input import GroundingNetInput
@@ -82,11 +83,10 @@ def test_engine_forward_vs_reference(tag, dtype, tol):
 
 
 @pytest.mark.parametrize("mode", [0, 2])
-def test_layernorm_statistics_sources_agree(mode, monkeypatch):
+def test_layernorm_statistics_sources_agree(mode):
     """The three ways the LN-folded GEMMs get (mu, rstd) -- from the producer's out_stats pass (mode 0), summed by the
     consumer itself (mode 2), the default mix (mode 1) -- are the same arithmetic on the same rows: the emulated forward
     must agree to fp32 round-off whichever buffers carry them (catches a stale or clobbered `st.stats`)."""
-    from instancediffusion_amd import engine as engine_mod
     gold = cases.load_golden("tiny_mask")
     meta = gold["meta"]
     cfg = cases.cfg_for(meta["cfg"], meta["variant"])
@@ -95,8 +95,7 @@ def test_layernorm_statistics_sources_agree(mode, monkeypatch):
     g = GroundingNetInput().prepare(inp["gb"])
     outs = {}
     for m in (1, mode):
-        monkeypatch.setattr(engine_mod, "LN_SELF_MODE", m)
-        eng = UNetEngine(model, ops=EmulOps(torch.float32), use_graphs=False)
+        eng = UNetEngine(model, ops=EmulOps(torch.float32), use_graphs=False, knobs=dataclasses.replace(EngineKnobs.from_env(), ln_self=m))
         with torch.no_grad():
             cond = eng.prepare_cond(inp["context"], g)
             outs[m] = eng.forward_cond(inp["x"], inp["t"], cond).clone()
@@ -170,7 +169,7 @@ def test_broadcast_mask_stack_is_tokenized_once():
 
 
 def test_fused_qkv_projection_equals_the_two_gemm_form():
-    """From ``engine.vt_min_n`` tokens per sample (round 5: 256; rounds 3-4: 1024) the engine issues ONE q | k | v GEMM whose last C
+    """From ``knobs.vt_min_n`` tokens per sample (round 5: 256; rounds 3-4: 1024) the engine issues ONE q | k | v GEMM whose last C
     columns land transposed in the batch-interleaved V^T image (``vt_out``, include/idf.h); below, and with IDF_VT_GLOBAL=0, the
     q | k GEMM plus the transposed-V GEMM it replaced.  Same forward every way (32x32 latent on the 3-level model: the 320-channel
     level has 1024 tokens, the 640-channel level 256, the last one 64), also against the CPU oracle; the fused call count is checked."""
@@ -197,8 +196,8 @@ def test_fused_qkv_projection_equals_the_two_gemm_form():
                 return _real(*a, **k)
             ops.gemm = counting
             eng = UNetEngine(model, ops=ops, use_graphs=False)
-            assert eng.vt_min_n == 256                      # the shipped default
-            eng.vt_global, eng.vt_min_n = vt_global, min_n
+            assert eng.knobs.vt_min_n == 256                # the shipped default
+            eng.knobs = dataclasses.replace(eng.knobs, vt_global=vt_global, vt_min_n=min_n)
             cond = eng.prepare_cond(ctx, grounding)
             outs.append(eng.forward_cond(x, t, cond))
             n_fused = sum(1 for p in eng._st_layers() if p["c"] == 320 or (p["c"] == 640 and min_n <= 256))
@@ -209,12 +208,11 @@ def test_fused_qkv_projection_equals_the_two_gemm_form():
     assert cases.rel_rms(outs[0], want) < 3e-4
 
 
-def test_fused_mlp_is_used_from_its_row_threshold_and_equals_the_two_gemm_form(monkeypatch):
+def test_fused_mlp_is_used_from_its_row_threshold_and_equals_the_two_gemm_form():
     """engine._ff sends the GEGLU feed-forward of a C = 320 block to the fused kernel (ops.mlp_geglu) only from
-    ``engine.MLP_MIN_M`` token rows up -- below, the kernel's 128-row tiles no longer fill the chip and the two GEMMs are faster
+    ``knobs.mlp_min_m`` token rows up -- below, the kernel's 128-row tiles no longer fill the chip and the two GEMMs are faster
     (profiles/r04_mlp_small_m.log).  Same forward either way; call counts checked (3-level model, 32x32 latent: the 320-channel
     level has 2 x 1024 rows)."""
-    import instancediffusion_amd.engine as E
     cfg = cases.cfg_for("test_box.yaml", "mid")
     model = build_model(cfg)
     g = torch.Generator().manual_seed(22)
@@ -226,27 +224,25 @@ def test_fused_mlp_is_used_from_its_row_threshold_and_equals_the_two_gemm_form(m
     outs, calls = [], []
     with torch.no_grad():
         for min_m in (2048, 2049):                               # M = 2 x 1024 rows at the 320-channel level
-            monkeypatch.setattr(E, "MLP_MIN_M", min_m)
             ops = EmulOps(torch.float32)
-            eng = UNetEngine(model, ops=ops, use_graphs=False)
+            eng = UNetEngine(model, ops=ops, use_graphs=False, knobs=dataclasses.replace(EngineKnobs.from_env(), mlp_min_m=min_m))
             cond = eng.prepare_cond(ctx, grounding)
             before = ops.calls.get("mlp_geglu", 0)
             outs.append(eng.forward_cond(x, t, cond))
             calls.append(ops.calls.get("mlp_geglu", 0) - before)
             n_top = sum(1 for p in eng._st_layers() if p["c"] == 320)
-    assert E.MLP_FUSED and calls == [2 * n_top, 0] and n_top > 0          # the fuser's feed-forward and the block's own, per layer
+    assert eng.knobs.mlp_fused and calls == [2 * n_top, 0] and n_top > 0          # the fuser's feed-forward and the block's own, per layer
     assert cases.rel_rms(outs[0], outs[1]) < 1e-5
 
 
 @pytest.mark.parametrize("fuser", [True, False])
-def test_paired_forward_hoists_the_conditioning_free_prefix_exactly(fuser, monkeypatch):
+def test_paired_forward_hoists_the_conditioning_free_prefix_exactly(fuser):
     """A guidance batch [cond | uncond] carries the same latent and timestep in both halves: with ``paired=True`` the engine
     runs the first conv, the first ResBlock and the first block's self-attention ONCE for the n distinct rows and duplicates
-    them behind the last layer that does not read the conditioning (engine.PAIR_HOIST).  Exact: the same bits as the forward
+    them behind the last layer that does not read the conditioning (``knobs.pair_hoist``).  Exact: the same bits as the forward
     over all 2n rows (batch-invariant emulator), with half the attention rows in that first self-attention; also with the
     fuser switched off (alpha = 0 stage), and equal to the CPU oracle."""
     from oracle import ref_cpu
-    from instancediffusion_amd import engine as engine_mod, synth
     from instancediffusion_amd.engine import Cond
     cfg = cases.cfg_for("test_box.yaml", "mid")
     model = build_model(cfg)
@@ -261,8 +257,8 @@ def test_paired_forward_hoists_the_conditioning_free_prefix_exactly(fuser, monke
     outs, rows = [], []
     with torch.no_grad():
         for hoist in (True, False):
-            monkeypatch.setattr(engine_mod, "PAIR_HOIST", hoist)
-            eng = UNetEngine(model, ops=EmulOps(torch.float32, batch_invariant=True), use_graphs=False)
+            eng = UNetEngine(model, ops=EmulOps(torch.float32, batch_invariant=True), use_graphs=False,
+                             knobs=dataclasses.replace(EngineKnobs.from_env(), pair_hoist=hoist))
             if not fuser:
                 eng.set_fuser_scale(0.0)
             pair = Cond.cat([eng.prepare_cond(ctx, grounding), eng.prepare_cond(uc, gi.get_null_input(batch=2))])
@@ -276,11 +272,10 @@ def test_paired_forward_hoists_the_conditioning_free_prefix_exactly(fuser, monke
     assert cases.rel_rms(outs[0][:2], want) < 3e-4
 
 
-def test_paired_flag_on_a_batch_that_is_not_a_guidance_pair_is_rejected(monkeypatch):
+def test_paired_flag_on_a_batch_that_is_not_a_guidance_pair_is_rejected():
     """VERDICT r4 / ADVICE r4: ``forward_cond(paired=True)`` trusts the caller that rows [n, 2n) repeat (x, t) of rows [0, n).
     The guarantee is verified when a launch configuration is first used (and on every call with IDF_DEBUG_PAIRED=1): a batch
     with different latents OR different timesteps in its halves raises instead of returning the hoisted (wrong) eps."""
-    from instancediffusion_amd import engine as engine_mod, synth
     from instancediffusion_amd.engine import Cond
     cfg = cases.cfg_for("test_box.yaml", "tiny")
     model = build_model(cfg)
@@ -303,26 +298,25 @@ def test_paired_flag_on_a_batch_that_is_not_a_guidance_pair_is_rejected(monkeypa
         # the same key again: not re-checked by default (no host sync per step) ...
         eng.forward_cond(x2, torch.cat([t, t]), pair, paired=True)
         # ... but on every call in debug mode
-        monkeypatch.setattr(engine_mod, "DEBUG_PAIRED", True)
+        eng.knobs = dataclasses.replace(eng.knobs, debug_paired=True)
         with pytest.raises(ValueError, match="paired=True"):
             eng.forward_cond(x2, torch.cat([t, t]), pair, paired=True)
         # without the flag the same batch is an ordinary 4-row forward
         assert torch.isfinite(eng.forward_cond(x2, torch.cat([t, t]), pair)).all()
         # the structural form -- the caller hands over the n DISTINCT rows and the engine writes both halves of its
         # input itself; nothing to verify, and the result is the full pair's, bit for bit (this is what the samplers do)
-        monkeypatch.setattr(engine_mod, "DEBUG_PAIRED", False)
+        eng.knobs = dataclasses.replace(eng.knobs, debug_paired=False)
         half = eng.forward_cond(x, t, pair, paired=True)
         assert tuple(half.shape) == (4, 4, 16, 16) and torch.equal(half, ok)
 
 
-def test_groupnorm_partials_travel_from_the_producing_conv_to_the_next_groupnorm(monkeypatch):
+def test_groupnorm_partials_travel_from_the_producing_conv_to_the_next_groupnorm():
     """Round 5: a 3x3 conv whose output feeds a GroupNorm leaves that GroupNorm's partial statistics (idf_conv3x3 gn_partial) and the
     GroupNorm only normalises.  The engine hands the partials from a producing conv to the layer that follows IMMEDIATELY -- ResBlock
     conv1 -> its second GroupNorm, ResBlock conv2 -> the SpatialTransformer's norm / the next ResBlock's first GroupNorm, Downsample ->
     the next ResBlock -- and drops them behind anything else: a SpatialTransformer rewrites its input buffer in place, and the decoder's
     first GroupNorm reads the ScaleU concat.  Checked: every partial a conv leaves is consumed by exactly one GroupNorm, the GroupNorms
     behind a SpatialTransformer / a concat run their own statistics pass, and the forward equals the IDF_GN_EPI=0 one to fp32 rounding."""
-    from instancediffusion_amd import engine as engine_mod, synth
     cfg = cases.cfg_for("test_box.yaml", "mid")
     model = build_model(cfg)
     g = torch.Generator().manual_seed(35)
@@ -334,9 +328,8 @@ def test_groupnorm_partials_travel_from_the_producing_conv_to_the_next_groupnorm
     outs, counts = [], []
     with torch.no_grad():
         for epi in (True, False):
-            monkeypatch.setattr(engine_mod, "GN_EPI", epi)
             ops = EmulOps(torch.float32)
-            eng = UNetEngine(model, ops=ops, use_graphs=False)
+            eng = UNetEngine(model, ops=ops, use_graphs=False, knobs=dataclasses.replace(EngineKnobs.from_env(), gn_epi=epi))
             cond = eng.prepare_cond(ctx, grounding)
             c0 = dict(ops.calls)
             outs.append(eng.forward_cond(x, t, cond))

@@ -85,13 +85,23 @@ def test_the_double_refuses_an_empty_capture_and_an_allocation_in_a_capture(monk
 
 def test_clip_and_vae_engines_load_without_the_unet_engine():
     """The shared base lives in ``engine_base``: a fresh interpreter imports the CLIP and VAE engines without ``engine`` (and its
-    ``host.unet``), so not even a value of ``IDF_LN_SELF`` that ``engine`` refuses at import reaches them."""
+    ``host.unet``), so a value of ``IDF_LN_SELF`` that the UNet engine refuses does not reach them.  Nor does it reach an import of
+    ``engine`` itself: the environment is read when a ``UNetEngine`` is constructed (``EngineKnobs.from_env``), and that raises."""
+    env = dict(os.environ, IDF_LN_SELF="7", HIP_VISIBLE_DEVICES="-1")
     code = ("import sys, instancediffusion_amd.clip_engine, instancediffusion_amd.vae_engine; "
             "bad = [m for m in ('instancediffusion_amd.engine', 'instancediffusion_amd.host.unet') if m in sys.modules]; "
             "print('loaded:', bad); sys.exit(1 if bad else 0)")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=REPO,
-                       env=dict(os.environ, IDF_LN_SELF="7", HIP_VISIBLE_DEVICES="-1"))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=REPO, env=env)
     assert r.returncode == 0 and "loaded: []" in r.stdout, r.stdout + r.stderr
+    code = ("import types, torch, instancediffusion_amd.engine as E\n"
+            "from tests.emul_ops import EmulOps\n"
+            "print('imported')\n"
+            "try:\n"
+            "    E.UNetEngine(types.SimpleNamespace(num_heads=8), ops=EmulOps(torch.float32), use_graphs=False)\n"
+            "except ValueError as e:\n"
+            "    print('refused:', e)\n")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=REPO, env=env)
+    assert r.returncode == 0 and "imported" in r.stdout and "refused: IDF_LN_SELF=7: must be 0, 1 or 2" in r.stdout, r.stdout + r.stderr
 
 
 # ---- deliberately wrong engines ---------------------------------------------------------------------------------------------------

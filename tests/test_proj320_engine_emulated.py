@@ -3,11 +3,13 @@ projections (``proj_row_takes``) makes the engine hand the cross-attention query
 Every combination of fuser on / off, paired forward or not, q | k | v row kernel on / off and fused / two-GEMM feed-forward must
 equal the forward of an engine whose ops object has no such kernel -- in particular the paired forward with the q | k | v row kernel
 off and the fuser's feed-forward unfused, where the statistics buffer is allocated BEHIND the duplication of the first layer."""
+import dataclasses
+
 import pytest
 import torch
 
 from grounding_input.text_grounding_tokinzer_input import GroundingNetInput
-from instancediffusion_amd.engine import Cond, UNetEngine
+from instancediffusion_amd.engine import Cond, EngineKnobs, UNetEngine
 from tests import cases
 from tests.emul_ops import EmulOps
 from tests.test_engine_emulated import build_model
@@ -32,10 +34,9 @@ class _Takes(EmulOps):
 @pytest.mark.parametrize("qkv_row", [True, False])
 @pytest.mark.parametrize("paired", [True, False])
 @pytest.mark.parametrize("fuser", [True, False])
-def test_handing_the_query_its_statistics_changes_nothing(fuser, paired, qkv_row, ff_fused, monkeypatch):
-    from instancediffusion_amd import engine as E, synth
-    monkeypatch.setattr(E, "QKV_ROW", qkv_row)
-    monkeypatch.setattr(E, "MLP_MIN_M", 0 if ff_fused else 1 << 30)
+def test_handing_the_query_its_statistics_changes_nothing(fuser, paired, qkv_row, ff_fused):
+    from instancediffusion_amd import synth
+    knobs = dataclasses.replace(EngineKnobs.from_env(), qkv_row=qkv_row, mlp_min_m=0 if ff_fused else 1 << 30)
     cfg = cases.cfg_for("test_box.yaml", "mid")
     model = build_model(cfg)
     g = torch.Generator().manual_seed(41)
@@ -48,7 +49,7 @@ def test_handing_the_query_its_statistics_changes_nothing(fuser, paired, qkv_row
     outs = []
     with torch.no_grad():
         for ops in (_Takes(torch.float32, batch_invariant=True), EmulOps(torch.float32, batch_invariant=True)):
-            eng = UNetEngine(model, ops=ops, use_graphs=False)
+            eng = UNetEngine(model, ops=ops, use_graphs=False, knobs=knobs)
             if not fuser:
                 eng.set_fuser_scale(0.0)
             pair = Cond.cat([eng.prepare_cond(ctx, grounding), eng.prepare_cond(uc, gi.get_null_input(batch=2))])
@@ -57,7 +58,7 @@ def test_handing_the_query_its_statistics_changes_nothing(fuser, paired, qkv_row
                 sts = [p for blk in eng.in_blocks + [eng.mid_block] + eng.out_blocks for p in blk if p["kind"] == "st" and p["c"] == 320]
                 n320 = len(sts)
                 fused_ff = ff_fused and all("w2p" in p["f_ff"] for p in sts) and ops.mlp_supported(4 * 256, 320)
-                want = 0 if (E.LN_SELF_MODE != 1 or (fuser and fused_ff)) else n320
+                want = 0 if (eng.knobs.ln_self != 1 or (fuser and fused_ff)) else n320
                 assert n320 > 0 and ops.handed == want, (ops.handed, want)
     assert torch.isfinite(outs[0]).all()
     assert cases.rel_rms(outs[0], outs[1]) < 1e-5

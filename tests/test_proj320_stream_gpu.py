@@ -12,6 +12,8 @@ out_stats are held to torch.var_mean (fp64) of the STORED 16-bit output.  The ke
 Shapes: M = the least the kernel takes on the box (two 256-row tiles per CU, the rule of qkv320w_kernel: 84 MB per matrix at 256 CUs),
 that + one 32-row block (an uneven tail across CUs), and 3.5 tiles per CU.
 """
+import dataclasses
+
 import pytest
 import torch
 
@@ -274,16 +276,16 @@ def test_mode_0_of_the_persistent_kernel_bypasses_every_row_kernel(lib):
         lib.idf_set_tuning(_lib.IDF_TUNE_GEMM_BIG, prev)
 
 
-def _query_handed(E, p, M, fuser, takes):
+def _query_handed(knobs, p, M, fuser, takes):
     """The test's own rule for the cross-attention query of an M-row C = 320 layer: its statistics are handed in (so the kernel can
-    take it) where the kernel takes M rows, the engine runs LN_SELF_MODE 1, and the producer in front of it is an idf_gemm epilogue:
+    take it) where the kernel takes M rows, the engine runs LN-self mode 1, and the producer in front of it is an idf_gemm epilogue:
     always with the fuser off (attn1's out-projection); with it on only where the fuser's feed-forward is NOT the fused MLP launch."""
-    ff_fused = "w2p" in p["f_ff"] and E.LN_SELF_MODE != 2 and M >= E.MLP_MIN_M and M % 128 == 0
-    return E.LN_SELF_MODE == 1 and takes(M) and not (fuser and ff_fused)
+    ff_fused = "w2p" in p["f_ff"] and knobs.ln_self != 2 and M >= knobs.mlp_min_m and M % 128 == 0
+    return knobs.ln_self == 1 and takes(M) and not (fuser and ff_fused)
 
 
 @pytest.mark.parametrize("case", ["fuser_on", "fuser_off", "paired_fuser_on_qkv_row_off_ff_unfused"])
-def test_engine_forward_knob_on_and_off(lib, case, monkeypatch):
+def test_engine_forward_knob_on_and_off(lib, case):
     """A reduced-width model (one ResBlock per level, three levels; C = 320 at the first) at a row count whose C = 320 level
     qualifies, knob on and off: both within the forward bar of the reference golden, and stat 8 = the number of qualifying sites
     counted from the layer list (per C = 320 SpatialTransformer: proj_in, attn1.out, attn2.out, proj_out; f_attn.out with the fuser on;
@@ -292,20 +294,19 @@ def test_engine_forward_knob_on_and_off(lib, case, monkeypatch):
     q | k | v projection then sums its own statistics: no producer in front of the duplication) and the fuser's feed-forward as two
     GEMMs: the query's statistics come from that feed-forward, into the buffer allocated BEHIND the duplication."""
     from grounding_input.text_grounding_tokinzer_input import GroundingNetInput
-    from instancediffusion_amd import _lib, engine as E
+    from instancediffusion_amd import _lib
     from instancediffusion_amd.engine import Cond
     from tests.test_engine_gpu import _build, _case, _check
     fuser = case != "fuser_off"
     paired = case.startswith("paired")
-    if paired:
-        monkeypatch.setattr(E, "QKV_ROW", False)
-        monkeypatch.setattr(E, "MLP_MIN_M", 1 << 30)
     gold, meta, cfg, inp = _case("mid_box")
     model = _build(cfg)
     gi = GroundingNetInput()
     model.grounding_tokenizer_input = gi
     g = {k: v.cuda() for k, v in gi.prepare(inp["gb"]).items()}
     eng = model.engine
+    if paired:
+        eng.knobs = dataclasses.replace(eng.knobs, qkv_row=False, mlp_min_m=1 << 30)
     L = meta["latent"]
     rows = -(-min_m(lib) // (L * L))
     rows += rows % 2
@@ -333,7 +334,7 @@ def test_engine_forward_knob_on_and_off(lib, case, monkeypatch):
                 sites = 0
                 for p in sts:
                     head = M // 2 if p is hoisted else M
-                    sites += 2 * int(takes(head)) + (2 + int(fuser)) * int(takes(M)) + int(_query_handed(E, p, M, fuser, takes))
+                    sites += 2 * int(takes(head)) + (2 + int(fuser)) * int(takes(M)) + int(_query_handed(eng.knobs, p, M, fuser, takes))
                 n0 = stat(lib, _lib.IDF_STAT_PROJ_ROW_LAUNCHES)
                 eps[knob] = eng.forward_cond(x, t, slot, paired=paired).float().cpu()
                 served = stat(lib, _lib.IDF_STAT_PROJ_ROW_LAUNCHES) - n0

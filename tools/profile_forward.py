@@ -28,7 +28,7 @@ cond = eng.prepare_cond(inputs[0]["context"], inputs[0]["grounding_input"])
 x = torch.randn(batch, 4, 64, 64, device=dev)
 t = torch.full((batch,), 500.0, device=dev)
 # the sampler's forwards are guidance pairs: rows [batch/2, batch) repeat the latent of rows [0, batch/2) and the engine computes
-# their conditioning-free prefix once (engine.PAIR_HOIST); PROFILE_UNPAIRED=1 profiles a forward of `batch` distinct rows
+# their conditioning-free prefix once (EngineKnobs.pair_hoist); PROFILE_UNPAIRED=1 profiles a forward of `batch` distinct rows
 paired = batch % 2 == 0 and os.environ.get("PROFILE_UNPAIRED") != "1"
 if paired:
     x[batch // 2:] = x[:batch // 2]

@@ -23,7 +23,7 @@ eng.use_graphs = False
 cond = eng.prepare_cond(inputs[0]["context"], inputs[0]["grounding_input"])
 x = torch.randn(batch, 4, 64, 64, device=dev)
 t = torch.full((batch,), 500.0, device=dev)
-# a guidance pair, as the samplers form their forwards (engine.PAIR_HOIST); PROFILE_UNPAIRED=1: `batch` distinct rows
+# a guidance pair, as the samplers form their forwards (EngineKnobs.pair_hoist); PROFILE_UNPAIRED=1: `batch` distinct rows
 paired = batch % 2 == 0 and os.environ.get("PROFILE_UNPAIRED") != "1"
 if paired:
     x[batch // 2:] = x[:batch // 2]
