@@ -1,7 +1,8 @@
 """Cases, input builders, fp64 references and the per-element bound for the matrix-core kernels behind ``idf_gemm``, ``idf_conv3x3`` and
 ``idf_conv3x3_down``: the small-tile kernels (with their split-K reducer), the latency ("ring") kernel and the persistent big-tile
 kernel.  No GPU and no HIP library: tests/test_gemm_conv_refs.py proves this module on the CPU, tests/test_gemm_conv_edges_gpu.py
-applies it to the kernels.
+applies it to the kernels, tests/test_gemm_big_walk_gpu.py to the persistent kernel where a workgroup walks several work items (the
+WALK_* cases and the mirror of the tile walk, at the end of this file).
 
 The references are written directly in torch on fp64 and share no code with tests/emul_ops.py.  Each takes the kernel's own inputs
 (the 16-bit tensors already rounded, the fp32 ones as they are) and upcasts them; each returns ``(want, slack)``.
@@ -300,7 +301,7 @@ def gemm_case(M, N, K, dt, epi="bias", kind="normal", batch=0, shared=None, ldo_
     kw = {}
     if epi not in ("res", "res_gate", "res_alias", "ln_col", "out_stats"):
         kw["bias"] = gen((N,), 710 + N)
-    if epi == "out_stats":                               # four rows of variance ~4e-6, below OUT_STATS_EPS: a missing eps shows there
+    if epi.endswith("out_stats"):                        # four rows of variance ~4e-6, below OUT_STATS_EPS: a missing eps shows there
         a[..., :4, :] = (a[..., :4, :].float() * 2.0 ** -9).to(T)
     if epi == "bias_rowbias":
         kw["rowbias"], kw["rows_per_batch"] = gen((-(-M // 50), N), 711).to(T), 50
@@ -317,7 +318,7 @@ def gemm_case(M, N, K, dt, epi="bias", kind="normal", batch=0, shared=None, ldo_
         kw["ln_row"] = (None, w.float().sum(-1))
     if epi == "ln_col":
         kw["ln_col"] = (row_stats32(w), a.float().sum(-1), gen((M,), 713))
-    return dict(a=a, w=w, kw=kw, f32out=epi == "f32out", out_stats=epi == "out_stats", res_alias=epi == "res_alias",
+    return dict(a=a, w=w, kw=kw, f32out=epi == "f32out", out_stats=epi.endswith("out_stats"), res_alias=epi.endswith("res_alias"),
                 ldo_pad=ldo_pad, ldr_pad=ldr_pad, ldrb_pad=ldrb_pad)
 
 
@@ -518,3 +519,214 @@ def all_cases(dt):
     for (B, H, W_, Cin, Cout) in DOWN_CASES:
         for res in (False, True):
             yield f"conv_down {(B, H, W_, Cin, Cout)} res={res}", "conv", conv_case((B, H, W_, Cin, Cout, 2, 0), dict(res=res), dt, pad_lo=0), False
+
+
+# ---- the persistent kernel's tile walk (csrc/gemm_big.hip) ---------------------------------------------------------------------------
+# A mirror of gemm_kernel_big's work-item arithmetic and of the hybrid plan of idf_launch_big, like ``split_plan`` not a measurement:
+# NUM_CU workgroup slots, a workspace that always fits.  The GPU cannot show which walk ran or which workgroup ran which item -- both
+# walks compute the same bits -- so what the walk cases below reach is proved here, on the CPU (tests/test_gemm_conv_refs.py), and
+# tests/test_gemm_big_walk_gpu.py judges only the results.
+BM_BIG = 256
+
+
+def big_tile_width(N, geglu=False, geglu_period=64):
+    """The BN idf_launch_big picks for N weight rows (packed rows for GEGLU); 0: the persistent kernel does not take it."""
+    if geglu:
+        return 320 if geglu_period == 32 and N % 320 == 0 else 256 if N % 256 == 0 else 0
+    return 320 if N % 320 == 0 else 256 if N % 256 == 0 else 128 if N % 128 == 0 else 0
+
+
+def big_tiles(M, N, bn):
+    return (N // bn) * -(-M // BM_BIG)
+
+
+def hybrid_plan(M, N, K, min_eff=80, num_cu=NUM_CU):
+    """The hybrid launch idf_launch_big makes of a plain GEMM / conv under IDF_TUNE_GEMM_BIG = 3 when its tile grid fills less than
+    ``min_eff`` % of the slots of its rounds: dict(whole, rem, S, tail_m0, items) -- ``whole`` leading whole-tile items, the remaining
+    ``rem`` tiles (rows from ``tail_m0``) cut into ``S`` K-slices each -- or None when it launches unsplit or declines."""
+    bn = big_tile_width(N)
+    tiles_n, tiles, nk = N // bn, big_tiles(M, N, bn), K // BK
+    rounds = -(-tiles // num_cu)
+    if tiles * 100 >= min_eff * rounds * num_cu or tiles * 2 <= num_cu or bn == 128:
+        return None                                      # at the bar: unsplit; half-empty grids are uniform split-K's (split_plan)
+    whole = ((tiles // num_cu) * num_cu // tiles_n) * tiles_n
+    rem = tiles - whole
+    if whole <= 0 or rem <= 0:
+        return None
+    for S in range(num_cu // rem, 1, -1):
+        if nk % S == 0 and nk // S >= 4:                 # slices of at least four K-tiles
+            return dict(whole=whole, rem=rem, S=S, tail_m0=whole // tiles_n * BM_BIG, items=whole + rem * S)
+    return None
+
+
+def big_walk_chunked(M, N, bn, hybrid=None, fold=False, num_cu=NUM_CU):
+    """Does the launch take the chunked walk (tile_walk == 1 and more items than workgroups)?"""
+    items = 4 * big_tiles(M, N, bn) if fold else big_tiles(M, N, bn)
+    return hybrid is None and N // bn >= 32 and items > min(items, num_cu)
+
+
+def big_walk(M, N, bn, hybrid=None, fold=False, num_cu=NUM_CU):
+    """For every workgroup (by blockIdx.x) the ordered work items (tile, slice) it runs.  ``hybrid`` = (full items, S) of a split
+    launch (its item_map: items below ``full`` are whole tiles, the rest S slices per tile); ``fold``: the four parity phases of
+    idf_conv_up2x_folded, phase-major -- "tile" is then phase * tiles + tile.  G = min(items, num_cu) workgroups; workgroup L takes
+    slot (L & 7) * (G >> 3) + (L >> 3) when G % 8 == 0, else L; slot s walks s, s + G, ... or, chunked, [s q + min(s, r), ...).
+    A mirror of the kernel's index arithmetic, not a measurement: no counter or output shows which walk a launch took."""
+    tiles = big_tiles(M, N, bn)
+    full, S = hybrid if hybrid is not None else (tiles, 1)
+    items = 4 * tiles if fold else full + (tiles - full) * S
+    G = min(items, num_cu)
+    chunked = big_walk_chunked(M, N, bn, hybrid, fold, num_cu)
+
+    def item_map(i):
+        return (i, 0) if i < full or fold else (full + (i - full) // S, (i - full) % S)
+    walk = []
+    for bid in range(G):
+        slot = (bid & 7) * (G >> 3) + (bid >> 3) if G % 8 == 0 else bid
+        if chunked:
+            q, r = divmod(items, G)
+            seq0 = slot * q + min(slot, r)
+            seq = range(seq0, seq0 + q + (1 if slot < r else 0))
+        else:
+            seq = range(slot, items, G)
+        walk.append([item_map(i) for i in seq])
+    return walk
+
+
+# Walk cases: the smallest M that gives at least NUM_CU + 2 work items and ends in a ragged last m-tile; K-tile counts that make
+# consecutive tiles enter the LDS ring on different stages (2 stages: an odd count; the 128-wide tiles' 3 stages: 2, 3 and 4).
+# (shape (M, N, K) with N the weight rows -- packed for GEGLU, q | k | v for the fused projection --, epilogue, work items)
+WALK_VT_COL0 = 640
+WALK_DENSE = [
+    ((32924, 640, 128), "bias_res_gate", 258),           # 320-wide plain, 2 K-tiles
+    ((32924, 640, 192), "bias_res_gate", 258),           # ... 3 K-tiles
+    ((32924, 640, 192), "f32out", 258),
+    ((32924, 512, 192), "bias", 258),                    # 256-wide plain
+    ((32924, 512, 192), "gelu_res_gate", 258),
+    ((22172, 384, 128), "bias_rowbias", 261),            # 128-wide, 3 stages: a tile enters the ring 2 ...
+    ((22172, 384, 192), "bias_rowbias", 261),            # ... 0 ...
+    ((22172, 384, 256), "bias_rowbias", 261),            # ... 1 stages (mod 3) behind its predecessor
+    ((32924, 640, 192), "ln_row_self", 258),             # LNS: statistics summed in the K loop, ln_stats_out checked
+    ((32924, 512, 192), "ln_row_self", 258),
+    ((32924, 640, 192), "bias_res_out_stats", 258),      # STATS: out_stats from the epilogue registers
+    ((32924, 512, 192), "bias_res_out_stats", 258),
+    ((22096, 960, 192), "vt", 261),                      # VT: fused q | k | V^T, statistics given; M % 16 == 0, M % 256 == 80
+    ((22096, 960, 192), "vt_self", 261),                 # VT + LNS
+    ((32924, 640, 192), "geglu32", 258),                 # GLU: period 32 on 320-wide tiles, statistics given
+    ((32924, 640, 192), "geglu32_self", 258),            # GLU + LNS
+    ((32924, 512, 192), "geglu64", 258),                 # period 64 on 256-wide tiles
+    ((2204, 10240, 128), "bias", 288),                   # chunked walk: 32 n-tiles of 320 per m-tile, 9 m-tiles ...
+    ((2204, 8192, 128), "bias", 288),                    # ... of 256 ...
+    ((2204, 10240, 128), "geglu32", 288),                # ... and the GLU kernel; 32 workgroups take two consecutive n-tiles
+]
+WALK_CHUNKED = [c for c in WALK_DENSE if c[0][0] == 2204]
+RB_RES = dict(rowbias=True, res=True)
+# ((B, H, W, Cin, Cout, stride, up), options, pad_lo, work items); Cin = 64: nine K-tiles
+WALK_CONV = [
+    ((3, 104, 106, 64, 640, 1, 0), RB_RES, 1, 260),      # 320-wide; 33072 rows, tiles straddle the samples
+    ((3, 208, 211, 64, 640, 2, 0), RB_RES, 1, 260),      # the same output through stride 2
+    ((3, 52, 53, 64, 640, 1, 1), RB_RES, 1, 260),        # ... through nearest-x2
+    ((3, 208, 212, 64, 640, 2, 0), dict(res=True), 0, 260),     # ... through idf_conv3x3_down (which has no row bias)
+    ((3, 104, 106, 64, 512, 1, 0), RB_RES, 1, 260),      # 256-wide
+    ((3, 148, 149, 64, 128, 1, 0), RB_RES, 1, 259),      # 128-wide, 3 stages; 66156 rows
+]
+# GST: gn_partial out of the epilogue.  Ho * Wo = 182 x 64, 34944 rows: 137 m-tiles x 2; a sample boundary falls on a 64-row chunk
+# inside a tile
+WALK_GST = ((3, 104, 112, 64, 640, 1, 0), dict(rowbias=True), 1, 274)
+WALK_FOLD = ((1, 129, 129, 64, 320), 264)                # idf_conv_up2x_folded: 66 m-tiles x 4 phases
+WALK_HYBRID_DENSE = ((33180, 640, 512), "bias_res_alias")      # 260 tiles, 256 whole + 4 x 2 slices of 4 K-tiles
+WALK_HYBRID_CONV = ((3, 104, 106, 128, 640, 1, 0), RB_RES)     # 18 K-tiles: 256 whole + 4 x 3 slices of 6
+WALK_HYBRID_EXPECTED = {
+    "dense": dict(whole=256, rem=4, S=2, tail_m0=32768, items=264),
+    "conv": dict(whole=256, rem=4, S=3, tail_m0=32768, items=268),
+}
+WALK_EXACT_DENSE = (32924, 640, 192)                     # integer operands, bit for bit: 320-wide dense, 320-wide conv, hybrid dense
+WALK_EXACT_CONV = (3, 104, 106, 64, 640, 1, 0)
+WALK_SAME_ROWS = [(32924, 640, 192), (32924, 512, 192), (22172, 384, 192)]    # A[m] = A[m % 256]: 320-, 256- and 128-wide
+
+
+def walk_dense_width(shape, epi):
+    return big_tile_width(shape[1], epi.startswith("geglu"), int(epi[5:7]) if epi.startswith("geglu") else 64)
+
+
+def walk_dense_case(shape, epi, dt, kind="normal"):
+    """The case dict of a WALK_DENSE entry (as ``gemm_case`` / ``geglu_case``); ``ln_stats_out`` / ``vt_col0`` name its by-products."""
+    M, N, Kk = shape
+    if epi.startswith("geglu"):
+        case = geglu_case(M, N, Kk, int(epi[5:7]), dt, kind)
+        if epi.endswith("_self"):
+            case["kw"]["ln_row"] = (None, case["kw"]["ln_row"][1])
+            case["ref_kw"]["ln_row"] = (None, case["ref_kw"]["ln_row"][1])
+            case["ln_stats_out"] = True
+        return case
+    if epi.startswith("vt"):
+        a, w = gemm_operands(M, N, Kk, dt, shift=0.5)
+        self_ln = epi == "vt_self"
+        kw = dict(bias=gen((N,), 710 + N), ln_row=(None if self_ln else row_stats32(a), w.float().sum(-1)))
+        return dict(a=a, w=w, kw=kw, vt_col0=WALK_VT_COL0, ln_stats_out=self_ln)
+    case = gemm_case(M, N, Kk, dt, epi, kind)
+    case["ln_stats_out"] = epi == "ln_row_self"
+    return case
+
+
+def walk_want(case, cd=torch.float64):
+    return want_of("geglu" if "ref_kw" in case else "gemm", case, cd)
+
+
+def same_rows_case(shape, dt):
+    """A[m] = A[m % 256]: every m-tile sees the same operand tile.  Bias only -- a per-row residual or row bias would tell the
+    rows apart."""
+    case = gemm_case(*shape, dt, "bias")
+    case["a"] = case["a"][torch.arange(shape[0]) % BM_BIG].contiguous()
+    return case
+
+
+def fold_case(shape, dt):
+    """idf_conv_up2x_folded: the fp32 3x3 image, folded in fp32 and rounded once (wf), and rounded unfolded (w) for the reference."""
+    from instancediffusion_amd.engine import pack_conv_up2x
+    B, H, W_, Cin, Cout = shape
+    w4 = gen((Cout, Cin, 3, 3), 741, (9 * Cin) ** -0.5)
+    T = DTYPES[dt]
+    return dict(x=gen((B, H, W_, Cin), 740).to(T), wf=pack_conv_up2x(w4).to(T), bias=gen((Cout,), 742),
+                w=w4.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin).to(T))
+
+
+def walk_launches():
+    """(label, M, N, tile width, hybrid (full, S) or None, fold, work items the tables claim, chunked?) of every walk case."""
+    for shape, epi, items in WALK_DENSE:
+        yield f"dense {shape} {epi}", shape[0], shape[1], walk_dense_width(shape, epi), None, False, items, shape[0] == 2204
+    for shape, opts, pad_lo, items in WALK_CONV + [WALK_GST]:
+        M, N, _, _ = conv_dispatch_args(shape, opts, pad_lo)
+        yield f"conv {shape} pad_lo={pad_lo}", M, N, big_tile_width(N), None, False, items, False
+    (B, H, W_, _, Cout), items = WALK_FOLD
+    yield "fold", B * H * W_, Cout, 320, None, True, items, False
+    (M, N, Kk), _ = WALK_HYBRID_DENSE
+    plan = hybrid_plan(M, N, Kk)
+    yield "hybrid dense", M, N, 320, (plan["whole"], plan["S"]), False, plan["items"], False
+    M, N, Kk, _ = conv_dispatch_args(*WALK_HYBRID_CONV)
+    plan = hybrid_plan(M, N, Kk)
+    yield "hybrid conv", M, N, 320, (plan["whole"], plan["S"]), False, plan["items"], False
+
+
+# ---- GroupNorm partials of a conv output ---------------------------------------------------------------------------------------------
+def gn_partial_errors(part, out):
+    """(mean, M2) per (sample, 64-row chunk, group) that a conv left in ``part`` [B, HW / 64, 32, 2] against fp64 statistics of the
+    16-bit output ``out`` [B, Ho, Wo, C] it stored, chunk by chunk: (largest mean error in units of the chunk's standard deviation,
+    largest relative M2 error)."""
+    B, C = out.shape[0], out.shape[-1]
+    v = out.double().cpu().reshape(B, -1, 64, 32, C // 32).permute(0, 1, 3, 2, 4).reshape(B, part.shape[1], 32, -1)
+    mean = v.mean(-1)
+    m2 = ((v - mean[..., None]) ** 2).sum(-1)
+    pc = part.double().cpu()
+    scale = (m2 / v.shape[-1]).sqrt().clamp_min(1e-3)           # per-chunk std
+    nan = lambda t: torch.where(torch.isnan(t), torch.full_like(t, float("inf")), t)
+    return float(nan((pc[..., 0] - mean).abs() / scale).max()), float(nan((pc[..., 1] - m2).abs() / m2.clamp_min(1e-6)).max())
+
+
+def same_rows_mismatch(out):
+    """Elements of a 16-bit ``out`` [M, N] whose bits differ from row m % 256's -- 0 when rows m and m % 256 were computed from the
+    same operands by the same arithmetic (every complete 256-row block, and the ragged last one against the head of the first)."""
+    bits = out.view(torch.int16)
+    M, full = out.shape[0], out.shape[0] // BM_BIG
+    first = bits[:BM_BIG]
+    bad = int((bits[:full * BM_BIG].reshape(full, BM_BIG, -1) != first).sum())
+    return bad + int((bits[full * BM_BIG:] != first[:M - full * BM_BIG]).sum())

@@ -10,137 +10,18 @@ leading dimension, all of which must still be NaN afterwards.  Each family is fo
 must show that it took the launch -- or, where the code says it declines the shape, that it did not.  The K-slices named in the
 [parity] lines come from the Python mirror of the dispatch code (checked on the CPU); the counters cannot show them.
 """
-import contextlib
-
 import pytest
 import torch
 
 from tests import gemm_conv_cases as K
+from tests.gemm_conv_run import DTS, cached, check, exact, gemm_takes, ops_for, run_conv, run_gemm
 
 pytestmark = pytest.mark.gpu
 
-DTS = ["bf16", "fp16"]
 FAMS = list(K.FAMILIES)
-_OPS, _REFS = {}, {}
-
-
-def ops_for(dt):
-    if dt not in _OPS:
-        from instancediffusion_amd.ops import HipOps
-        _OPS[dt] = HipOps(K.DTYPES[dt])
-    return _OPS[dt]
-
-
-def cached(key, build):
-    """A case and its fp64 reference, computed once and shared by the families that run it (never modified)."""
-    if key not in _REFS:
-        _REFS[key] = build()
-    return _REFS[key]
-
-
-@contextlib.contextmanager
-def forced(lib, family):
-    """Force a kernel family; yields a function that returns the (persistent, latency) launches since."""
-    from instancediffusion_amd import _lib
-    big, ring = K.FAMILIES[family]
-    prev_big = lib.idf_set_tuning(_lib.IDF_TUNE_GEMM_BIG, big)
-    prev_ring = lib.idf_set_tuning(_lib.IDF_TUNE_GEMM_RING, ring)
-    stats = lambda: (lib.idf_get_stat(_lib.IDF_STAT_GEMM_BIG_LAUNCHES), lib.idf_get_stat(_lib.IDF_STAT_GEMM_RING_LAUNCHES))
-    start = stats()
-    try:
-        yield lambda: tuple(a - b for a, b in zip(stats(), start))
-    finally:
-        lib.idf_set_tuning(_lib.IDF_TUNE_GEMM_RING, prev_ring)
-        lib.idf_set_tuning(_lib.IDF_TUNE_GEMM_BIG, prev_big)
-
-
-def assert_family(family, takes, launches, what):
-    want = {"small": (0, 0), "ring": (0, 1), "big": (1, 0)}[family] if takes else (0, 0)
-    assert launches == want, f"{what}: {family} family {'must take' if takes else 'must decline'} the launch; (persistent, latency) " \
-                             f"launches {launches}"
-
-
-def padded(t, pad):
-    """``t`` on the GPU as a view of rows ``pad`` elements longer, the spare columns NaN."""
-    if not pad:
-        return t.cuda()
-    buf = torch.full(tuple(t.shape[:-1]) + (t.shape[-1] + pad,), float("nan"), dtype=t.dtype, device="cuda")
-    buf[..., :t.shape[-1]] = t.cuda()
-    return buf[..., :t.shape[-1]]
-
-
-def check(entry, dt, family, label, got, want, slack, guard, f32out=False):
-    torch.cuda.synchronize()
-    bad, ratio = K.outside(got, want, slack, dt, f32out)
-    em, er = K.relmax(got, want), K.rel_rms(got, want)
-    print(f"[parity] {entry} {dt} {family} {label}: err/bound {ratio:.3f} relmax {em:.2e} rel-rms {er:.2e} outside {bad}")
-    assert guard() == "", f"stored outside the output view: {guard()}"
-    assert bool(torch.isfinite(got).all()), "non-finite output"
-    assert bad == 0, f"{bad} of {want.numel()} elements outside the bound (worst error / bound {ratio:.3f})"
-    if want.numel() >= K.RMS_MIN_ELEMS:
-        assert er < K.RMS_BAR[dt]
-
-
-def exact(what, got, want, guard):
-    """Bit for bit, with its [parity] line: the number of elements whose bits differ and the largest difference among them."""
-    torch.cuda.synchronize()
-    got = got.cpu()
-    bad = got.view(torch.int16) != want.view(torch.int16)
-    bad &= ~((got == 0) & (want == 0))                       # +0 and -0 are the same result
-    worst = float((got.double() - want.double())[bad].abs().nan_to_num(nan=float("inf")).max()) if bool(bad.any()) else 0.0
-    print(f"[parity] {what}: bit for bit, {int(bad.sum())} of {want.numel()} differ, largest difference {worst:.3g}")
-    assert guard() == "", f"stored outside the output view: {guard()}"
-    assert not bool(bad.any()), [(i, float(got[tuple(i)]), float(want[tuple(i)])) for i in bad.nonzero().tolist()[:8]]
 
 
 # ---- idf_gemm ------------------------------------------------------------------------------------------------------------------
-def run_gemm(ops, case, family, what, takes, w_key="w"):
-    """Launch the case under the forced family: -> (out view, guard check, out_stats or None)."""
-    a, w = case["a"].cuda(), case[w_key].cuda()
-    kw = dict(case["kw"])
-    geglu = kw.get("geglu", False)
-    M, N = a.shape[-2], w.shape[-2] // (2 if geglu else 1)
-    lead = tuple(max(a.shape[:-2], w.shape[:-2]))
-    out, guard = K.guarded(lead + (M, N), torch.float32 if case.get("f32out") else ops.dtype, "cuda", ld=N + case.get("ldo_pad", 0))
-    for k in ("bias", "gate"):
-        if k in kw:
-            kw[k] = kw[k].cuda()
-    if "rowbias" in kw:
-        kw["rowbias"] = padded(kw["rowbias"], case.get("ldrb_pad", 0))
-    if "res" in kw:
-        if case.get("res_alias"):
-            out.copy_(kw["res"].cuda())
-            kw["res"] = out
-        else:
-            kw["res"] = padded(kw["res"], case.get("ldr_pad", 0))
-    for k in ("ln_row", "ln_col"):
-        if k in kw:
-            kw[k] = tuple(None if t is None else t.cuda().contiguous() for t in kw[k])
-    stats = sguard = None
-    if case.get("out_stats"):
-        stats, sguard = K.guarded((M, 2), torch.float32, "cuda")
-        kw["out_stats"] = stats
-    with forced(ops.lib, family) as launches:
-        ops.gemm(a, w, out, **kw)
-        torch.cuda.synchronize()
-        assert_family(family, takes, launches(), what)
-    if sguard is not None:
-        assert sguard() == "", "out_stats stored outside its [M, 2]"
-    return out, guard, stats
-
-
-def gemm_takes(family, case, w_key="w"):
-    kw = case["kw"]
-    M, Kk = case["a"].shape[-2:]
-    N = case[w_key].shape[-2]
-    batch = max(case["a"].dim(), case[w_key].dim()) == 3
-    cols = N // 2 if kw.get("geglu") else N
-    return K.family_takes(family, M, N, Kk, geglu=kw.get("geglu", False), geglu_period=kw.get("geglu_period", 64),
-                          batch=3 if batch else 1, self_ln="ln_row" in kw and kw["ln_row"][0] is None,
-                          ldo=cols + case.get("ldo_pad", 0), ldr=cols + case.get("ldr_pad", 0) if "res" in kw else None,
-                          ld_rowbias=N + case.get("ldrb_pad", 0) if "rowbias" in kw else None)
-
-
 def gemm_test(dt, family, label, build, require_takes=True):
     ops = ops_for(dt)
     case, want, slack = cached((label, dt), build)
@@ -303,38 +184,6 @@ def test_families_decline_what_the_code_says(family, shape, opts, dt):
 
 
 # ---- idf_conv3x3, idf_conv3x3_down -----------------------------------------------------------------------------------------------
-def run_conv(ops, case, family, what, takes):
-    x = case["x"]
-    if x.is_contiguous():
-        xd = x.cuda()
-    else:                                                    # a channel slice: keep the wide rows
-        base = x._base.cuda()
-        xd = base[..., x.storage_offset():x.storage_offset() + x.shape[-1]]
-        assert xd.stride() == x.stride()
-    kw = dict(case["kw"])
-    pad_lo, up = kw.pop("pad_lo"), kw.pop("up")
-    B, Ho, Wo, Cout = case["out_shape"]
-    nv = kw.get("n_valid", 0)
-    if nv:
-        out, guard = K.guarded((B, nv, Ho, Wo), torch.float32, "cuda")
-    else:
-        out, guard = K.guarded((B, Ho, Wo, Cout), ops.dtype, "cuda", ld=Cout + case["ldo_pad"])
-    for k in ("bias", "rowbias"):
-        if k in kw:
-            kw[k] = kw[k].cuda()
-    if "res" in kw:
-        kw["res"] = padded(kw["res"], case["ldr_pad"])
-    with forced(ops.lib, family) as launches:
-        if pad_lo == 0:
-            kw.pop("stride")
-            ops.conv3x3_down(xd, case["w"].cuda(), out, **kw)
-        else:
-            ops.conv3x3(xd, case["w"].cuda(), out, upsample=up, **kw)
-        torch.cuda.synchronize()
-        assert_family(family, takes, launches(), what)
-    return out, guard
-
-
 def conv_test(dt, family, shape, opts, kind="normal", pad_lo=1):
     ops = ops_for(dt)
     label = f"{shape} {opts} {kind}"

@@ -316,3 +316,200 @@ def test_the_out_stats_tolerance_rejects_wrong_statistics(dt):
         bad = stats(got32)
         bad[7, 0] = float("nan")
         assert K.out_stats_excess(bad, want, slack, dt)[0] == float("inf")
+
+
+# ---- the persistent kernel's tile walk -----------------------------------------------------------------------------------------------
+def _is_partition(walk, items):
+    flat = [it for wg in walk for it in wg]
+    return len(flat) == len(items) and set(flat) == set(items) and len(set(flat)) == len(flat)
+
+
+def _items(M, N, bn, hybrid=None, fold=False):
+    tiles = K.big_tiles(M, N, bn)
+    if fold:
+        return [(t, 0) for t in range(4 * tiles)]
+    if hybrid is None:
+        return [(t, 0) for t in range(tiles)]
+    full, S = hybrid
+    return [(t, 0) for t in range(full)] + [(t, s) for t in range(full, tiles) for s in range(S)]
+
+
+def test_the_walk_mirror_partitions_the_work_items():
+    """Every work item of every walk case runs on exactly one workgroup, under both walks, with and without the XCD permutation
+    (G = 250 is no multiple of 8), whole launches, hybrid ones and the folded launch's four phases."""
+    n = 0
+    for label, M, N, bn, hybrid, fold, items, _ in K.walk_launches():
+        walk = K.big_walk(M, N, bn, hybrid, fold)
+        assert len(walk) == K.NUM_CU and _is_partition(walk, _items(M, N, bn, hybrid, fold)), label
+        assert sum(len(wg) for wg in walk) == items, (label, "the work items the case table claims")
+        n += 1
+    assert n == len(K.WALK_DENSE) + len(K.WALK_CONV) + 4
+    for G in (8, 250, 256):                                  # synthetic grids: ragged rounds, one item per slot, many rounds
+        for (M, N, bn, hybrid, fold) in [(256 * 7, 640, 320, None, False), (256 * 300 + 5, 320, 320, None, False), (256 * 3, 10240, 320, None, False),
+                                         (256 * 33 + 9, 8192, 256, None, False), (256 * 9, 384, 128, None, False), (256 * 140, 640, 320, (256, 3), False),
+                                         (256 * 70, 320, 320, None, True), (256, 320, 320, None, False)]:
+            walk = K.big_walk(M, N, bn, hybrid, fold, num_cu=G)
+            want = _items(M, N, bn, hybrid, fold)
+            assert len(walk) == min(G, len(want)) and _is_partition(walk, want), (G, M, N, bn, hybrid, fold)
+            assert max(map(len, walk)) - min(map(len, walk)) <= 1
+    # the XCD permutation: with G % 8 == 0 workgroup L takes slot (L & 7) * G / 8 + (L >> 3); the identity otherwise
+    assert [wg[0][0] for wg in K.big_walk(256 * 16, 320, 320, num_cu=16)] == [0, 2, 4, 6, 8, 10, 12, 14, 1, 3, 5, 7, 9, 11, 13, 15]
+    assert [wg[0][0] for wg in K.big_walk(256 * 10, 320, 320, num_cu=10)] == list(range(10))
+    assert K.big_walk(256 * 5, 10240, 320, num_cu=64)[8] == [(3, 0), (4, 0), (5, 0)]         # chunked: 160 tiles, q = 2, r = 32; workgroup 8 has slot 1
+    assert K.big_walk(256 * 5, 640, 320, num_cu=8)[1] == [(1, 0), (9, 0)]                    # strided: slot 1 of G = 8, 10 tiles
+
+
+def test_walk_cases_follow_their_rule():
+    """At least NUM_CU + 2 work items and at most NUM_CU + 32, a ragged last m-tile, some workgroup with two items; the
+    chunked cases get the chunked walk and no other does; consecutive tiles enter the LDS ring on different stages."""
+    for label, M, N, bn, hybrid, fold, items, chunked in K.walk_launches():
+        walk = K.big_walk(M, N, bn, hybrid, fold)
+        assert items >= K.NUM_CU + 2 and M % 256 != 0, label
+        assert max(map(len, walk)) >= 2, label
+        assert K.big_walk_chunked(M, N, bn, hybrid, fold) == chunked, label
+        assert items <= K.NUM_CU + 32, label                 # a second round of a few tiles, no more
+    for shape, epi, _ in K.WALK_CHUNKED:                     # 32 workgroups take two consecutive n-tiles of one m-tile
+        walk = K.big_walk(shape[0], shape[1], K.walk_dense_width(shape, epi))
+        two = [wg for wg in walk if len(wg) == 2]
+        assert len(two) == 32 and all(b[0] == a[0] + 1 and a[0] // 32 == b[0] // 32 for a, b in two)
+    # ring stages: the 2-stage kernels' tiles enter on the other stage when the K-tile count is odd (all but the K = 128 case, kept
+    # for its two K-tiles); the 3-stage kernel's at 2, 0 and 1 stages (mod 3) behind
+    assert sorted({s[2] // 64 % 3 for s, e, _ in K.WALK_DENSE if s[1] == 384}) == [0, 1, 2]
+    assert all(s[2] // 64 % 2 == 1 for s, e, _ in K.WALK_DENSE if s[1] != 384 and s[2] != 128)
+    assert all(9 * s[3] // 64 == 9 for s, _, _, _ in K.WALK_CONV + [K.WALK_GST])
+    for shape, epi, _ in K.WALK_DENSE:                       # the persistent kernel takes each, on the tile width its comment names
+        geglu = epi.startswith("geglu")
+        assert K.family_takes("big", *shape, geglu=geglu, geglu_period=32 if "32" in epi else 64, self_ln=epi.endswith("self")), (shape, epi)
+        assert K.split_plan("big", *shape, geglu=geglu) == [shape[2] // 64]
+    assert [K.walk_dense_width(s, e) for s, e, _ in K.WALK_DENSE] == [320, 320, 320, 256, 256, 128, 128, 128, 320, 256, 320, 256, 320, 320, 320, 320,
+                                                                     256, 320, 256, 320]
+    # the fused q | k | v case: whole 320-wide tiles on either side of vt_col0, 16-token stores
+    (M, N, _), _, _ = K.WALK_DENSE[12]
+    assert N % 320 == 0 and K.WALK_VT_COL0 % 320 == 0 and 0 < K.WALK_VT_COL0 < N and M % 16 == 0 and M % 256 == 80
+    # GST: whole 64-row chunks per sample, groups inside a wave's 160 columns, and a sample boundary inside a tile
+    (B, H, W_, _, Cout, _, _), _, _, _ = K.WALK_GST
+    assert (H * W_) % 64 == 0 and 160 % (Cout // 32) == 0 and (H * W_) % 256 == 128
+    for shape in K.WALK_SAME_ROWS:
+        assert any(s == shape for s, _, _ in K.WALK_DENSE)
+
+
+def test_hybrid_plans_are_what_the_case_comments_claim():
+    (M, N, Kk), _ = K.WALK_HYBRID_DENSE
+    assert K.hybrid_plan(M, N, Kk) == K.WALK_HYBRID_EXPECTED["dense"]
+    Mc, Nc, Kc, kw = K.conv_dispatch_args(*K.WALK_HYBRID_CONV)
+    assert Kc // 64 == 18 and K.hybrid_plan(Mc, Nc, Kc) == K.WALK_HYBRID_EXPECTED["conv"] and K.family_takes("big", Mc, Nc, Kc, **kw)
+    for (m, n, plan) in ((M, N, K.WALK_HYBRID_EXPECTED["dense"]), (Mc, Nc, K.WALK_HYBRID_EXPECTED["conv"])):
+        walk = K.big_walk(m, n, 320, (plan["whole"], plan["S"]))
+        both = [wg for wg in walk if len(wg) == 2]
+        assert len(both) == plan["rem"] * plan["S"]          # e.g. eight workgroups run a whole tile and then a slice
+        assert all(a[0] < plan["whole"] and a[1] == 0 and b[0] >= plan["whole"] for a, b in both)
+        assert {it for wg in both for it in wg[1:]} == {(t, s) for t in range(plan["whole"], plan["whole"] + plan["rem"]) for s in range(plan["S"])}
+        assert plan["tail_m0"] % 256 == 0 and plan["tail_m0"] < m
+    # what test_big_kernel_hybrid_tail_split's comments say of its shapes: 288 tiles -> 5 slices of 4; 576 tiles -> 2 slices; K = 320: none
+    assert K.hybrid_plan(18 * 4096, 320, 1280)["S"] == 5 and K.hybrid_plan(18 * 4096, 640, 640)["S"] == 2
+    assert K.hybrid_plan(18 * 4096, 320, 320) is None
+    # a grid at or above the bar launches unsplit
+    assert K.hybrid_plan(256 * 230, 320, 1280) is None
+
+
+def _second_round_tile(M, N, bn, num_cu=K.NUM_CU):
+    """(tile, the tile its workgroup ran before it) -- the first such pair whose tiles both have all 256 rows."""
+    tiles_n = N // bn
+    for wg in K.big_walk(M, N, bn, num_cu=num_cu):
+        for (prev, _), (tile, _) in zip(wg, wg[1:]):
+            if (tile // tiles_n + 1) * 256 <= M and (prev // tiles_n + 1) * 256 <= M:
+                return tile, prev
+    raise AssertionError("no workgroup runs two whole tiles")
+
+
+def _block(tile, N, bn):
+    m_tile, n_tile = divmod(tile, N // bn)
+    return slice(m_tile * 256, m_tile * 256 + 256), slice(n_tile * bn, n_tile * bn + bn)
+
+
+def _walk_failure_models(want, y_last, M, N, bn, num_cu=K.NUM_CU):
+    """The three failures the walk cases aim at, applied to a correct result ``want`` [M, N] (fp64; the epilogue is linear in the
+    accumulator) whose last K-tile contributes ``y_last``: -> name -> mutated result."""
+    tile, prev = _second_round_tile(M, N, bn, num_cu)
+    (r, c), (rp, cp) = _block(tile, N, bn), _block(prev, N, bn)
+    stale = want.clone()                                     # the last K-tile of `tile` read from a ring stage that still holds `prev`'s
+    stale[r, c] += y_last[rp, cp] - y_last[r, c]
+    moved = want.clone()                                     # the tile's block stored at the position of its n-neighbour
+    n_tile = tile % (N // bn)
+    cn = _block(tile - n_tile + (n_tile + 1) % (N // bn), N, bn)[1]
+    moved[r, cn] = want[r, c]
+    skipped = want.clone()                                   # one wave's 64-row strip never stored
+    skipped[r.start + 64:r.start + 128, c] = float("nan")
+    return dict(stale=stale, moved=moved, skipped=skipped), (tile, prev)
+
+
+@pytest.mark.parametrize("dt", DTS)
+def test_the_bound_rejects_the_walk_failures_dense(dt):
+    """The 128-wide walk case (22172, 384, 192): the reference rounded to the type is inside the bound; a stale ring stage, a
+    misplaced block and a skipped wave are outside.  On identical rows (A[m] = A[m % 256]) the stale stage breaks the equality of
+    the 256-row blocks: the tile follows, in its workgroup, a tile of ANOTHER n-tile, so the stale operands are other weights."""
+    shape, epi, _ = K.WALK_DENSE[6]
+    M, N, Kk = shape
+    assert (shape, epi) == ((22172, 384, 192), "bias_rowbias")
+    case = K.walk_dense_case(shape, epi, dt)
+    want, slack = K.walk_want(case)
+    T = K.DTYPES[dt]
+    assert K.outside(want.to(T), want, slack, dt)[0] == 0
+    y_last = case["a"][:, Kk - 64:].double() @ case["w"][:, Kk - 64:].double().t()
+    models, (tile, prev) = _walk_failure_models(want, y_last, M, N, 128)
+    assert tile % 3 != prev % 3
+    for name, got in models.items():
+        assert K.outside(got.to(T), want, slack, dt)[0] > 0, name
+    same = K.same_rows_case(shape, dt)
+    want, _ = K.gemm_want(same)
+    good = want[:256].repeat(-(-M // 256), 1)[:M].contiguous()       # what identical arithmetic on identical rows stores
+    assert K.same_rows_mismatch(good.to(T)) == 0
+    y_last = same["a"][:, Kk - 64:].double() @ same["w"][:, Kk - 64:].double().t()
+    stale = _walk_failure_models(good, y_last, M, N, 128)[0]["stale"]
+    assert K.same_rows_mismatch(stale.to(T)) > 0
+    ragged = good.clone()                                    # ... and the ragged last block is compared too
+    ragged[-1, 5] += 1.0
+    assert K.same_rows_mismatch(ragged.to(T)) == 1
+
+
+@pytest.mark.parametrize("dt", DTS)
+def test_the_bound_rejects_the_walk_failures_conv(dt):
+    """The 320-wide conv walk case (64 -> 640, bias + row bias + residual; its last K-tile is tap (2, 2)), shrunk for the CPU to
+    3 x 20 x 22 pixels on a mirror of 8 workgroups: 12 tiles, the ninth a whole tile behind tile 0, samples straddling tiles."""
+    (_, _, _, Cin, Cout, stride, up), opts, pad_lo, _ = K.WALK_CONV[0]
+    shape = (3, 20, 22, Cin, Cout, stride, up)
+    case = K.conv_case(shape, opts, dt, pad_lo=pad_lo)
+    want, slack = K.conv_want(case)
+    M, N, Kk, _ = K.conv_dispatch_args(shape, opts, pad_lo)
+    assert K.big_tiles(M, N, 320) == 8 + 4 and M % 256 != 0 and (20 * 22) % 256 != 0
+    T = K.DTYPES[dt]
+    assert K.outside(want.to(T), want, slack, dt)[0] == 0
+    w_last = torch.zeros_like(case["w"])
+    w_last[:, Kk - 64:] = case["w"][:, Kk - 64:]
+    y_last, _ = K.conv3x3_ref(case["x"], w_last, stride=stride, up=up, pad_lo=pad_lo)
+    models, (tile, prev) = _walk_failure_models(want.reshape(M, N), y_last.reshape(M, N), M, N, 320, num_cu=8)
+    assert (tile, prev) == (8, 0)
+    for name, got in models.items():
+        assert K.outside(got.to(T), want, slack, dt)[0] > 0, name
+
+
+def test_gn_partial_errors_sees_wrong_partials():
+    """The comparison test_conv3x3_gn_partial and the GST walk case share: exact partials give ~0; a chunk's mean off by 1e-4 of
+    its standard deviation, an M2 off by 0.1 % and a NaN are over its tolerances (2e-5, 2e-4)."""
+    out = K.gen((2, 8, 16, 64), 750).to(torch.bfloat16)
+    v = out.double().reshape(2, 2, 64, 32, 2).permute(0, 1, 3, 2, 4).reshape(2, 2, 32, 128)
+    mean = v.mean(-1)
+    part = torch.stack([mean, ((v - mean[..., None]) ** 2).sum(-1)], -1).float()
+    e_mean, e_m2 = K.gn_partial_errors(part, out)
+    assert e_mean < 1e-6 and e_m2 < 1e-6
+    bad = part.clone()
+    bad[1, 1, 7, 0] += 1e-4 * float(v[1, 1, 7].std())
+    assert K.gn_partial_errors(bad, out)[0] > 2e-5
+    bad = part.clone()
+    bad[0, 1, 31, 1] *= 1.001
+    assert K.gn_partial_errors(bad, out)[1] > 2e-4
+    bad = part.clone()
+    bad[0, 0, 0, 0] = float("nan")
+    assert K.gn_partial_errors(bad, out)[0] == float("inf")
+    swapped = part.flip(1)                                   # the chunks of a sample in the wrong order
+    assert K.gn_partial_errors(swapped, out)[0] > 2e-5

@@ -1430,6 +1430,7 @@ def test_conv3x3_gn_partial(ref, dt, B, H, Cin, Cout, stride, extra, epi_path):
     from instancediffusion_amd import _lib
     from instancediffusion_amd.engine import pack_conv3x3
     from instancediffusion_amd.ops import HipOps
+    from tests.gemm_conv_cases import gn_partial_errors
     ops = HipOps(dt)
     lib = _lib.load()
     x = (gen((B, H, H, Cin), 120) * 0.5).to(dt)
@@ -1457,14 +1458,7 @@ def test_conv3x3_gn_partial(ref, dt, B, H, Cin, Cout, stride, extra, epi_path):
     assert torch.equal(out, plain), "asking for the statistics must not change the conv output"
     assert torch.isfinite(part).all()
     # (a) fp64 statistics of the stored output
-    cpg = Cout // 32
-    v = out.double().cpu().reshape(B, -1, 64, 32, cpg).permute(0, 1, 3, 2, 4).reshape(B, shape[1], 32, -1)
-    mean = v.mean(-1)
-    m2 = ((v - mean[..., None]) ** 2).sum(-1)
-    pc = part.double().cpu()
-    scale = (m2 / v.shape[-1]).sqrt().clamp_min(1e-3)           # per-chunk std
-    mean_err = float(((pc[..., 0] - mean).abs() / scale).max())
-    m2_err = float(((pc[..., 1] - m2).abs() / m2.clamp_min(1e-6)).max())
+    mean_err, m2_err = gn_partial_errors(part, out)
     print(f"[parity] conv gn_partial B{B} {H}^2 {Cin}->{Cout} s{stride} {dt} epilogue={epi_path}: mean err {mean_err:.2e} std, M2 rel err {m2_err:.2e}")
     assert mean_err < 2e-5 and m2_err < 2e-4
     # (b) GroupNorm from the partials vs its own statistics pass

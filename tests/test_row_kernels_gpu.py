@@ -16,7 +16,7 @@ import pytest
 import torch
 
 from tests import row_kernel_cases as R
-from tests.test_gemm_conv_edges_gpu import exact, padded
+from tests.gemm_conv_run import exact, padded
 
 pytestmark = pytest.mark.gpu
 
