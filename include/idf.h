@@ -462,6 +462,22 @@ enum { IDF_CLIP_SRC_U8 = 0, IDF_CLIP_SRC_F32 = 1 };
 int idf_clip_crop_resize(const void* src, int kind, int B, int H, int W, const int* crops, int Ncrop, const int* tables, int Ntab,
                          const float* lut, float* out, int S, int K, void* stream);
 
+/* ---- instance masks on the device (host/masks.py; the reference decodes COCO RLE with pycocotools and resizes with Pillow NEAREST on
+ * the host, utils/input.py:161-186).  Added within ABI 5: a new symbol only.
+ * idf_rle_decode_planes: M jobs, one launch.  Job m decodes the run-length mask whose CUMULATIVE run ends are
+ *   ends[run_begin[m] .. run_end[m]) (uint32, runs alternate 0, 1, 0, .. over the column-major pixel index p = x * h + y of the
+ *   h x w = src_hw[m][0] x src_hw[m][1] source; zero-length runs are legal; a p behind the last end reads 0) and writes plane
+ *   dst_plane[m] of out (fp32 [P][S][S]) in full: out[plane][Y][X] = 0.0f / 1.0f, the value of source pixel sy = ((2Y + 1) h) / (2S),
+ *   sx = ((2X + 1) w) / (2S) in integer arithmetic -- Pillow's Image.resize((S, S), NEAREST).  Planes no job names are not touched.
+ *   area[m] (int32 [M]) is INCREMENTED by the number of ones job m wrote: the caller zeroes it.  Several jobs may share one run range.
+ * All tables are DEVICE memory and cannot be read here: the host validates them (host/masks.pack_masks); the kernel checks every
+ *   entry where it becomes an address, and a job with run_begin < 0, run_begin > run_end, run_end > n_ends, dst_plane outside [0, P),
+ *   h or w < 1, h * w >= 2^31 or S * max(h, w) >= 2^31 writes nothing.
+ * IDF_E_ARG: a null pointer, M < 0, n_ends < 0, P < 1, S < 1; IDF_E_UNSUPPORTED: S % 4, P * S * S >= 2^31, M > 65535; IDF_E_ALIGN: out
+ *   not 16-B aligned, a table not 4-B aligned.  All before any launch; M == 0 launches nothing and returns 0. */
+int idf_rle_decode_planes(const unsigned* ends, int n_ends, const int* run_begin, const int* run_end, const int* src_hw,
+                          const int* dst_plane, int M, float* out, int P, int S, int* area, void* stream);
+
 /* ---- layout helpers ---------------------------------------------------------------------------------------*/
 int idf_cast_f32_to_16(const float* x, void* out, long long n, int dtype, void* stream);
 

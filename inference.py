@@ -17,6 +17,10 @@ Two neighbours of the path need assets that do not exist offline; both are handl
   * weights: ``--ckpt instancediffusion_sd15.pth`` goes through ``utils.checkpoint.load_model_ckpt`` (ema -> model
     fallback, autoencoder / text_encoder / diffusion sub-dicts); without it ``--synthetic_weights`` must be given.
 The SDXL-refiner cascade (``--cascade_strength``, diffusers + downloads) is outside the path.
+
+``--instance_masks json`` makes the JSON's ``mask`` entries (COCO run-length masks) condition generation, as the reference's
+``eval_local.py`` route does (utils/input.py:161-186); the reference's ``inference.py`` decodes them and throws them away (:249), which
+stays the default (``ignore``).  The masks are decoded and resized on the device (``idf_rle_decode_planes``): only run lengths are uploaded.
 """
 from __future__ import annotations
 
@@ -64,11 +68,13 @@ class ClipPhraseEncoder:
 
 
 def get_model_inputs(meta, gi, text_encoder, phrase_encoder, num_images, device, starting_noise, negative_prompt=None,
-                     instance_input=False, use_masked_att=False):
+                     instance_input=False, use_masked_att=False, batch=None):
     """inference.py:39-78.  ``use_masked_att``: also build the box-shaped visibility planes and hand them to the model
-    (``eval_local.py --use_masked_att``; the reference's inference.py builds them but never passes them on)."""
-    batch = prepare_batch(meta, batch=num_images, max_objs=MAX_OBJS, model=phrase_encoder, processor=None,
-                          image_size=starting_noise.shape[-1], use_masked_att=use_masked_att, device=device)
+    (``eval_local.py --use_masked_att``; the reference's inference.py builds them but never passes them on).  ``batch``: the
+    ``prepare_batch`` result when the caller already has it (``--instance_masks json`` prepares all rows in one call)."""
+    if batch is None:
+        batch = prepare_batch(meta, batch=num_images, max_objs=MAX_OBJS, model=phrase_encoder, processor=None,
+                              image_size=starting_noise.shape[-1], use_masked_att=use_masked_att, device=device)
     context = text_encoder.encode([meta["prompt"]] * num_images).to(device)
     uc = None
     if not instance_input:
@@ -140,6 +146,20 @@ def clip_scores(args, images: torch.Tensor, data: dict, dtype, input_json=None, 
                 mean=round(sum(means) / len(means), 6))
 
 
+def report_masks(path: str, areas) -> None:
+    """``--instance_masks json``: one line per layout -- how many instances carried a mask, and which masks are empty."""
+    have = [i for i, a in enumerate(areas) if a >= 0]
+    empty = [i for i in have if areas[i] == 0]
+    print(f"masks {path}: {len(have)} of {len(areas)} instances carry a mask"
+          + (f"; area 0 (no conditioning): instances {empty}" if empty else "; none is empty"))
+
+
+def refuse_dropped_masks(args, model) -> None:
+    if args.instance_masks == "json" and model.position_net.eval_drops()[4]:
+        raise SystemExit(f"--instance_masks json: the model config ({args.test_config}) drops masks (test_drop_masks), so the JSON's "
+                         "masks would do nothing; use a config that keeps them (configs/test_mask.yaml)")
+
+
 def layout_folders(paths) -> list:
     """Output folder name per input JSON: its stem; a stem seen before gets a numeric suffix (a.json, x/a.json -> a, a_2)."""
     seen, out = {}, []
@@ -157,7 +177,9 @@ def run_layouts(args, paths, model, autoencoder, diffusion, gi, text_encoder, ph
     OUTPUT/<save_folder_name>/<json stem>/ with its own ``latents.pt`` / ``clip_scores.json``; ``--keep_best`` applies per layout."""
     datas = [json.load(open(p)) for p in paths]
     save_folder_name = f"gc{args.guidance_scale}-seed{args.seed}-alpha{args.alpha}"
-    metas = [meta_from_demo_json(d, args.alpha, ckpt=args.ckpt, save_folder_name=save_folder_name) for d in datas]
+    metas = [meta_from_demo_json(d, args.alpha, ckpt=args.ckpt, save_folder_name=save_folder_name, instance_masks=args.instance_masks)
+             for d in datas]
+    ops = model.engine.ops if args.instance_masks == "json" else None      # the masks are decoded on the device
     torch.manual_seed(args.seed)
     starting_noise = torch.randn(args.num_images, 4, model.image_size, model.image_size).to(dev)
     noises = [starting_noise] * len(paths)
@@ -166,13 +188,17 @@ def run_layouts(args, paths, model, autoencoder, diffusion, gi, text_encoder, ph
     K = args.num_images
     if args.mis > 0:
         sampler = PLMSSamplerInst(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale, mis=args.mis)
-        layouts = prepare_layout_inputs(metas, noises, gi, text_encoder, phrase_encoder, instances=True, max_objs=MAX_OBJS, device=dev)
+        layouts = prepare_layout_inputs(metas, noises, gi, text_encoder, phrase_encoder, instances=True, max_objs=MAX_OBJS, device=dev,
+                                        ops=ops)
+        areas = [lay[0].get("mask_areas") for lay in layouts]
         try:
             samples = sampler.sample_layouts(S=args.steps, layouts=layouts, uc=uc, guidance_scale=args.guidance_scale)
         except ValueError as e:
             raise SystemExit(str(e))
     else:
-        inp = prepare_layout_inputs(metas, noises, gi, text_encoder, phrase_encoder, instances=False, max_objs=MAX_OBJS, device=dev)
+        inp = prepare_layout_inputs(metas, noises, gi, text_encoder, phrase_encoder, instances=False, max_objs=MAX_OBJS, device=dev,
+                                    ops=ops)
+        areas = inp.get("mask_areas", [None] * len(paths))
         n = K * len(paths)
         extra = {}
         if args.sampler == "ddim":
@@ -182,6 +208,9 @@ def run_layouts(args, paths, model, autoencoder, diffusion, gi, text_encoder, ph
             sampler = PLMSSampler(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale)
         samples = sampler.sample(S=args.steps, shape=(n, model.in_channels, model.image_size, model.image_size), input=inp,
                                  uc=uc.expand(n, -1, -1), guidance_scale=args.guidance_scale, **extra)
+    if args.instance_masks == "json":
+        for path, meta, a in zip(paths, metas, areas):
+            report_masks(path, a if a is not None else [-1] * len(meta["phrases"]))
     loaded = {}
     for l, (path, stem) in enumerate(zip(paths, layout_folders(paths))):
         lat = samples[l * K:(l + 1) * K]
@@ -230,6 +259,9 @@ def main():
     ap.add_argument("--save_latents", action="store_true")
     ap.add_argument("--use_masked_att", action="store_true",
                     help="masked gated self-attention (attention.py:187-255): instance patches only see their own box")
+    ap.add_argument("--instance_masks", choices=["ignore", "json"], default="ignore",
+                    help="json: condition on the COCO run-length masks of the JSON's annos (decoded on the device); ignore: as the "
+                         "reference script, which decodes them and throws them away")
     ap.add_argument("--clip_score", choices=["hf", "hip"], default=None,
                     help="score every instance crop of every image against its phrase (local CLIP score) and write clip_scores.json "
                          "next to the PNGs; hip: crop, resize and both CLIP towers on the HIP kernels, from the decoder output on the device")
@@ -278,12 +310,14 @@ def main():
         from utils.checkpoint import load_model_ckpt
         model, autoencoder, clip_text, diffusion, cfg = load_model_ckpt(args.ckpt, args, args.device)
         use_clip = (args.text_encoder or "clip") == "clip"
+        refuse_dropped_masks(args, model)
     elif args.synthetic_weights:
         from instancediffusion_amd import synth
         cfg = load_yaml(args.test_config)
         with torch.device("meta"):
             model = instantiate_from_config(cfg["model"])
             autoencoder = instantiate_from_config(cfg["autoencoder"])
+        refuse_dropped_masks(args, model)
         model.load_state_dict(synth.synth_state_dict({k: tuple(v.shape) for k, v in model.state_dict().items()}),
                               assign=True)
         model.first_conv_sd_override = synth.synth_first_conv_sd()
@@ -313,7 +347,7 @@ def main():
         return run_layouts(args, paths, model, autoencoder, diffusion, gi, text_encoder, phrase_encoder, dev, dtype)
     data = json.load(open(args.input_json))
     save_folder_name = f"gc{args.guidance_scale}-seed{args.seed}-alpha{args.alpha}"
-    meta = meta_from_demo_json(data, args.alpha, ckpt=args.ckpt, save_folder_name=save_folder_name)
+    meta = meta_from_demo_json(data, args.alpha, ckpt=args.ckpt, save_folder_name=save_folder_name, instance_masks=args.instance_masks)
     torch.manual_seed(args.seed)
     starting_noise = torch.randn(args.num_images, 4, model.image_size, model.image_size).to(dev)
     inpaint = {}
@@ -324,8 +358,17 @@ def main():
         x0 = autoencoder.encode(image.to(dev))
         inpaint = dict(mask=keep.to(dev).expand(args.num_images, -1, -1, -1), x0=x0.expand(args.num_images, -1, -1, -1))
 
+    rows = None
+    if args.instance_masks == "json":
+        # every row of the call -- the global input and, under the Multi-instance Sampler, one per instance -- in ONE prepare_batch:
+        # their mask stacks come from one idf_rle_decode_planes launch
+        if args.mis > 0:
+            meta["instance_meta"] = [prepare_instance_meta(meta, i) for i in range(len(meta["phrases"]))]
+        rows = prepare_batch(meta, batch=args.num_images, max_objs=MAX_OBJS, model=phrase_encoder, processor=None,
+                             image_size=starting_noise.shape[-1], use_masked_att=args.use_masked_att, device=dev, ops=model.engine.ops)
+        report_masks(args.input_json, rows.get("mask_areas", [-1] * len(meta["phrases"])))
     inp, uc = get_model_inputs(meta, gi, text_encoder, phrase_encoder, args.num_images, dev, starting_noise,
-                               args.negative_prompt, use_masked_att=args.use_masked_att)
+                               args.negative_prompt, use_masked_att=args.use_masked_att, batch=rows)
     ag = partial(alpha_generator, type=meta["alpha_type"])
     shape = (args.num_images, model.in_channels, model.image_size, model.image_size)
     if args.mis > 0:
@@ -333,7 +376,8 @@ def main():
         inputs = [inp]
         for i in range(len(meta["phrases"])):
             inst, _ = get_model_inputs(prepare_instance_meta(meta, i), gi, text_encoder, phrase_encoder, args.num_images,
-                                       dev, starting_noise, instance_input=True, use_masked_att=args.use_masked_att)
+                                       dev, starting_noise, instance_input=True, use_masked_att=args.use_masked_att,
+                                       batch=None if rows is None else rows["instance_meta"][i])
             inputs.append(inst)
         samples = sampler.sample(S=args.steps, shape=shape, input=inputs, uc=uc, guidance_scale=args.guidance_scale)
     else:

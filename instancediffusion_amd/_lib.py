@@ -107,6 +107,7 @@ SYMBOLS = {
     "idf_attention_qkv": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, cf, ci, vp]),
     "idf_clip_patchify": (ci, [vp, vp, ci, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
     "idf_clip_crop_resize": (ci, [vp, ci, ci, ci, ci, vp, ci, vp, ci, vp, vp, ci, ci, vp]),
+    "idf_rle_decode_planes": (ci, [vp, ci, vp, vp, vp, vp, ci, vp, ci, ci, vp, vp]),
 }
 
 _lib = None

@@ -395,6 +395,45 @@ class HipOps:
                                                  _p(lut), _p(out), S, int(K), self._stream()), "idf_clip_crop_resize")
         return out
 
+    def rle_decode_planes(self, table, dst_plane, out, area=None, zero=True):
+        """``idf_rle_decode_planes``: ``table`` = ``host.masks.pack_masks(..)`` of the call's M jobs (host numpy arrays, validated
+        there and checked against ``out`` here, then uploaded: a few hundred run ends per mask), ``dst_plane``: M ints, the plane of
+        ``out`` fp32 [.., S, S] (contiguous, its leading dims flattened to P planes) that job m fills with its mask, decoded and
+        nearest-resized to S x S, bit for bit ``host.masks.decode_rle_reference``.  ``zero``: clear ``out`` first, so that planes no
+        job names are zero.  -> (out, area int32 [M] on the device: the ones each job wrote)."""
+        import numpy as np
+        ends, rb, re, hw = (np.ascontiguousarray(table[k]) for k in ("ends", "run_begin", "run_end", "src_hw"))
+        dst = np.ascontiguousarray(np.asarray(dst_plane, dtype=np.int64))
+        M, S = int(rb.shape[0]), int(out.shape[-1])
+        P = out.numel() // (S * S) if S else 0
+        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() >= 2 and out.shape[-2] == S):
+            raise ValueError("rle_decode_planes: out must be a contiguous fp32 [.., S, S] tensor on the device")
+        if S < 1 or S % 4 or P * S * S >= 2 ** 31:
+            raise ValueError(f"rle_decode_planes: S = {S} must be a positive multiple of 4 and out smaller than 2^31 elements")
+        if not (ends.dtype == np.uint32 and rb.dtype == np.int32 and re.dtype == np.int32 and hw.dtype == np.int32):
+            raise ValueError("rle_decode_planes: not a pack_masks table")
+        if re.shape != (M,) or hw.shape != (M, 2) or dst.shape != (M,):
+            raise ValueError(f"rle_decode_planes: {M} jobs need {M} run ranges, source sizes and destination planes")
+        if M and (rb.min() < 0 or (rb > re).any() or re.max() > ends.size or dst.min() < 0 or dst.max() >= P or hw.min() < 1
+                  or int(hw.max()) * S >= 2 ** 31 or len(set(dst.tolist())) != M):
+            raise ValueError("rle_decode_planes: a run range, source size or destination plane is out of range, or a plane is named twice")
+        if area is None:
+            area = torch.zeros(M, dtype=torch.int32, device=out.device)
+        else:
+            assert area.is_cuda and area.dtype == torch.int32 and area.is_contiguous() and area.numel() == M
+            area.zero_()
+        if zero:
+            out.zero_()
+        if M == 0:
+            return out, area
+        ints = np.concatenate([rb, re, hw.reshape(-1), dst.astype(np.int32), ends.view(np.int32)])      # one upload
+        dev = torch.from_numpy(ints).to(out.device)
+        base, n_ends = dev.data_ptr(), int(ends.size)
+        at = lambda k: C.c_void_p(base + 4 * k * M)                                                      # noqa: E731
+        _lib.check(self.lib.idf_rle_decode_planes(C.c_void_p(base + 20 * M), n_ends, at(0), at(1), at(2), at(4), M, _p(out), P, S,
+                                                  _p(area), self._stream()), "idf_rle_decode_planes")
+        return out, area
+
     def groupnorm(self, x, out, gamma, beta, eps, silu, partial=None):
         """x/out [B, HW, C] (or [B,H,W,C]) contiguous.  ``partial``: the statistics of x are already there ([B, nchunks, 32, 2]
         fp32 (mean, M2) per row chunk, as a conv3x3 leaves them): only the normalise pass runs."""
