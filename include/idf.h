@@ -357,6 +357,26 @@ int idf_ddim_update(const float* x, const float* eps_cond, const float* eps_unco
                     float* x_prev, float* pred_x0 /* or NULL */, long long n, void* stream);
 int idf_q_sample_blend(const float* x0, const float* noise, const float* mask, const float* img, float sqrt_ac, float sqrt_1m_ac,
                        float* out, int B, int C, long long HW, int mask_channels /* 1 or C */, void* stream);
+/* The same two launches over WORK UNITS (DDIMSamplerInst: the Multi-instance Sampler on DDIM steps).  Added within ABI 5: new symbols
+ * only.  A forward of phase 1 advances U units, several of them trajectories of the same image; the per-image operands (the step
+ * noise; the inpainting x0, its mask and its q_sample noise) stay [B] rows and are read through img_of: DEVICE int32 [U], unit u
+ * belongs to image img_of[u].  The launcher cannot read the table: the kernel clamps every entry it loads to [0, B-1], so a wrong
+ * table cannot send a load outside the per-image buffers.  Same device functions, same rounding, same access policy (16-B accesses
+ * where every pointer is 16-B aligned and chw % 4 == 0 -- and HW % 4 == 0 under a channel-broadcast mask -- else scalar, decided per
+ * launch); no allocation, no synchronisation; hipGraph-capturable; x_prev may alias x, out may alias img.
+ * idf_ddim_update_units: x, eps_cond, eps_uncond, x_prev, pred_x0: [U][chw]; noise: [B][chw] or NULL (sigma_t == 0).  idf_ddim_update's
+ *   expression with noise[img_of[u]] in place of noise[u].  img_of may be NULL when noise is NULL (nothing is per image) or when
+ *   U == B (unit u is image u): the launch is then idf_ddim_update's own kernel, bit for bit.  IDF_E_ARG before any launch: every
+ *   case of idf_ddim_update, U < 1, B < 1, chw < 1, noise != NULL with img_of == NULL and U != B.
+ * idf_q_sample_blend_units: img, out: [U][C][HW]; x0, noise: [B][C][HW]; mask: [B][mask_channels][HW]; row img_of[u] of the three for
+ *   unit u.  IDF_E_ARG before any launch: every case of idf_q_sample_blend, U < 1, B < 1, img_of == NULL. */
+int idf_ddim_update_units(const float* x, const float* eps_cond, const float* eps_uncond /* NULL = unguided */, float guidance,
+                          float a_t, float a_prev, float sigma_t, float sqrt_1m_at, const float* noise /* [B][chw]; NULL iff sigma_t == 0 */,
+                          const int* img_of /* device int32 [U], or NULL */, float* x_prev, float* pred_x0 /* or NULL */, int U, int B,
+                          long long chw, void* stream);
+int idf_q_sample_blend_units(const float* x0, const float* noise, const float* mask, const float* img, const int* img_of,
+                             float sqrt_ac, float sqrt_1m_ac, float* out, int U, int B, int C, long long HW,
+                             int mask_channels /* 1 or C */, void* stream);
 
 /* ---- Multi-instance Sampler merge (plms_instance.py:112-135) ---------------------------------------------
  * lat: [n_inst+1][B][C][H][W] fp32.  mode 0: mean over the first dim; mode 1: crop-and-paste of instance j's

@@ -8,7 +8,9 @@ caption}]) and the same call sequence as the reference (inference.py:165-309): d
 
 Beyond the reference's flags: ``--sampler ddim`` (+ ``--ddim_eta``) runs ``DDIMSampler`` (ldm/models/diffusion/ddim.py) instead of
 ``PLMSSampler``, and ``--init_image`` / ``--inpaint_mask`` reach the samplers' ``mask`` / ``x0`` arguments (plms.py:99-104,
-ddim.py:94-98): the image is encoded by ``AutoencoderKL.encode``, the mask is pooled to the latent grid.
+ddim.py:94-98): the image is encoded by ``AutoencoderKL.encode``, the mask is pooled to the latent grid.  ``--sampler ddim_inst`` runs
+``DDIMSamplerInst``, the Multi-instance Sampler (``--mis`` > 0) on DDIM steps: ``--ddim_eta`` and inpainting work under it, with one or
+several ``--input_json`` (the one image / mask pair then applies to every layout).
 
 Two neighbours of the path need assets that do not exist offline; both are handled explicitly, never silently:
   * text encoding (CLIP-L/14: ``ldm/modules/encoders``, ``utils/model.py:12-18``): with ``--ckpt`` the checkpoint's
@@ -35,7 +37,7 @@ import torch
 from instancediffusion_amd.host.alpha import alpha_generator, set_alpha_scale
 from instancediffusion_amd.host.config import instantiate_from_config, load_yaml
 from instancediffusion_amd.host.input import meta_from_demo_json, prepare_batch, prepare_instance_meta, prepare_layout_inputs
-from instancediffusion_amd.host.samplers import DDIMSampler, PLMSSampler, PLMSSamplerInst
+from instancediffusion_amd.host.samplers import DDIMSampler, DDIMSamplerInst, PLMSSampler, PLMSSamplerInst
 
 MAX_OBJS = 30
 
@@ -170,6 +172,16 @@ def layout_folders(paths) -> list:
     return out
 
 
+def load_inpaint(args, model, autoencoder, dev):
+    """``--init_image`` / ``--inpaint_mask`` -> (keep mask [1, 1, h, w], x0 [1, 4, h, w]) on the device, or None."""
+    if args.init_image is None:
+        return None
+    size = 8 * model.image_size
+    image, keep = load_init_image(args.init_image, size), latent_mask(args.inpaint_mask, size)
+    # the posterior sample times scale_factor (autoencoder.py:27-31), its noise the next draw of the CPU default generator
+    return keep.to(dev), autoencoder.encode(image.to(dev))
+
+
 def run_layouts(args, paths, model, autoencoder, diffusion, gi, text_encoder, phrase_encoder, dev, dtype):
     """Several ``--input_json``: different layouts, ``--num_images`` images each, sampled in ONE batch (``sample_layouts``; with
     ``--mis 0`` one row-stacked ``PLMSSampler`` / ``DDIMSampler`` call).  Every layout gets the starting noise a single-JSON run
@@ -187,12 +199,20 @@ def run_layouts(args, paths, model, autoencoder, diffusion, gi, text_encoder, ph
     ag = partial(alpha_generator, type=metas[0]["alpha_type"])
     K = args.num_images
     if args.mis > 0:
-        sampler = PLMSSamplerInst(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale, mis=args.mis)
+        extra = {}
+        if args.sampler == "ddim_inst":
+            sampler = DDIMSamplerInst(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale, mis=args.mis)
+            extra["eta"] = args.ddim_eta or 0.
+            inpaint = load_inpaint(args, model, autoencoder, dev)
+            if inpaint is not None:                                        # the one image / mask pair applies to every layout
+                extra.update(masks=[inpaint[0]] * len(paths), x0s=[inpaint[1]] * len(paths))
+        else:
+            sampler = PLMSSamplerInst(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale, mis=args.mis)
         layouts = prepare_layout_inputs(metas, noises, gi, text_encoder, phrase_encoder, instances=True, max_objs=MAX_OBJS, device=dev,
                                         ops=ops)
         areas = [lay[0].get("mask_areas") for lay in layouts]
         try:
-            samples = sampler.sample_layouts(S=args.steps, layouts=layouts, uc=uc, guidance_scale=args.guidance_scale)
+            samples = sampler.sample_layouts(S=args.steps, layouts=layouts, uc=uc, guidance_scale=args.guidance_scale, **extra)
         except ValueError as e:
             raise SystemExit(str(e))
     else:
@@ -270,18 +290,22 @@ def main():
                          "and no path, a key-seeded synthetic CLIP model")
     ap.add_argument("--keep_best", type=int, default=None,
                     help="write only the K images with the best mean CLIP score (needs --clip_score; the JSON still lists all)")
-    ap.add_argument("--sampler", choices=["plms", "ddim"], default="plms",
-                    help="ddim: DDIMSampler (ldm/models/diffusion/ddim.py) instead of PLMSSampler; without the Multi-instance Sampler")
+    ap.add_argument("--sampler", choices=["plms", "ddim", "ddim_inst"], default="plms",
+                    help="ddim: DDIMSampler (ldm/models/diffusion/ddim.py) instead of PLMSSampler; without the Multi-instance Sampler.  "
+                         "ddim_inst: DDIMSamplerInst, the Multi-instance Sampler (--mis > 0) on DDIM steps")
     ap.add_argument("--ddim_eta", type=float, default=None,
-                    help="--sampler ddim: eta of the DDIM variance schedule (default 0: deterministic; 1: DDPM-like)")
+                    help="--sampler ddim / ddim_inst: eta of the DDIM variance schedule (default 0: deterministic; 1: DDPM-like)")
     ap.add_argument("--init_image", type=str, default=None,
                     help="inpainting: PNG of the sampled size whose kept region is held to the original (needs --inpaint_mask)")
     ap.add_argument("--inpaint_mask", type=str, default=None,
                     help="inpainting: grey-scale PNG of the sampled size, >= 128 keeps the original, < 128 is repainted")
     args = ap.parse_args()
     paths = list(args.input_json)
+    ddim_inst = args.sampler == "ddim_inst"
+    if ddim_inst and not args.mis > 0:
+        raise SystemExit("--sampler ddim_inst is the Multi-instance Sampler on DDIM steps: give --mis > 0 (or --sampler ddim)")
     if len(paths) > 1:
-        if args.init_image is not None or args.inpaint_mask is not None:
+        if (args.init_image is not None or args.inpaint_mask is not None) and not ddim_inst:
             raise SystemExit("inpainting (--init_image / --inpaint_mask) takes one --input_json")
         if args.use_masked_att:
             raise SystemExit("--use_masked_att takes one --input_json: the mask / no-mask decision is per layout call")
@@ -289,13 +313,13 @@ def main():
         args.input_json = paths[0]                                         # one path: exactly the single-layout run
     if args.sampler == "ddim" and args.mis > 0:
         raise SystemExit("--sampler ddim has no Multi-instance Sampler (the reference has none): give --mis 0")
-    if args.ddim_eta is not None and args.sampler != "ddim":
+    if args.ddim_eta is not None and args.sampler not in ("ddim", "ddim_inst"):
         raise SystemExit("--ddim_eta needs --sampler ddim")
     if args.ddim_eta is not None and args.ddim_eta < 0:
         raise SystemExit("--ddim_eta must be >= 0")
     if (args.init_image is None) != (args.inpaint_mask is None):
         raise SystemExit("inpainting needs both --init_image and --inpaint_mask")
-    if args.init_image is not None and args.mis > 0:
+    if args.init_image is not None and args.mis > 0 and not ddim_inst:
         raise SystemExit("inpainting (--init_image / --inpaint_mask) runs without the Multi-instance Sampler: give --mis 0")
     if args.keep_best is not None and (args.clip_score is None or args.keep_best < 1):
         raise SystemExit("--keep_best K needs --clip_score and K >= 1")
@@ -351,12 +375,9 @@ def main():
     torch.manual_seed(args.seed)
     starting_noise = torch.randn(args.num_images, 4, model.image_size, model.image_size).to(dev)
     inpaint = {}
-    if args.init_image is not None:
-        size = 8 * model.image_size
-        image, keep = load_init_image(args.init_image, size), latent_mask(args.inpaint_mask, size)
-        # the posterior sample times scale_factor (autoencoder.py:27-31), its noise the next draw of the CPU default generator
-        x0 = autoencoder.encode(image.to(dev))
-        inpaint = dict(mask=keep.to(dev).expand(args.num_images, -1, -1, -1), x0=x0.expand(args.num_images, -1, -1, -1))
+    loaded = load_inpaint(args, model, autoencoder, dev)
+    if loaded is not None:
+        inpaint = dict(mask=loaded[0].expand(args.num_images, -1, -1, -1), x0=loaded[1].expand(args.num_images, -1, -1, -1))
 
     rows = None
     if args.instance_masks == "json":
@@ -372,14 +393,19 @@ def main():
     ag = partial(alpha_generator, type=meta["alpha_type"])
     shape = (args.num_images, model.in_channels, model.image_size, model.image_size)
     if args.mis > 0:
-        sampler = PLMSSamplerInst(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale, mis=args.mis)
+        extra = {}
+        if ddim_inst:
+            sampler = DDIMSamplerInst(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale, mis=args.mis)
+            extra = dict(inpaint, eta=args.ddim_eta or 0.)
+        else:
+            sampler = PLMSSamplerInst(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale, mis=args.mis)
         inputs = [inp]
         for i in range(len(meta["phrases"])):
             inst, _ = get_model_inputs(prepare_instance_meta(meta, i), gi, text_encoder, phrase_encoder, args.num_images,
                                        dev, starting_noise, instance_input=True, use_masked_att=args.use_masked_att,
                                        batch=None if rows is None else rows["instance_meta"][i])
             inputs.append(inst)
-        samples = sampler.sample(S=args.steps, shape=shape, input=inputs, uc=uc, guidance_scale=args.guidance_scale)
+        samples = sampler.sample(S=args.steps, shape=shape, input=inputs, uc=uc, guidance_scale=args.guidance_scale, **extra)
     else:
         if args.sampler == "ddim":
             sampler = DDIMSampler(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale)

@@ -277,17 +277,27 @@ __device__ __forceinline__ void ddim_elem(float x, float ec, float eu, bool guid
   if (noisy) { const float s = sigma * nz; r = r + s; }                               // :128-129
 }
 
-template <int V>
+// UNITS (idf_ddim_update_units): the rows are U work units of chw elements and the step noise is one row per IMAGE, [B][chw]: unit u
+// reads row img_of[u] of it, the entry clamped to [0, B-1] (a wrong table cannot send a load outside nz).  V == 4: chw % 4 == 0, so
+// a vector never crosses a unit.  !UNITS: img_of / chw / B are unused and the noise row is the element's own.
+template <int V, bool UNITS>
 __global__ void ddim_kernel(const float* x, const float* __restrict__ ec, const float* __restrict__ eu, float g, float s1m,
                             float sqrt_at, float sqrt_aprev, float dc, float sigma, const float* __restrict__ nz, float* xo,
-                            float* __restrict__ p0, long long n) {
+                            float* __restrict__ p0, long long n, const int* __restrict__ img_of, long long chw, int B) {
   static_assert(V == 1 || V == 4, "scalar or 16-B accesses");
   const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * V;
   if (i >= n) return;                                                                 // V == 4: the launcher guarantees n % 4 == 0
+  long long ni = i;                                                                   // the element's place in nz
+  if constexpr (UNITS) {
+    if (nz) {
+      const long long u = i / chw;
+      ni = (long long)min(max(img_of[u], 0), B - 1) * chw + (i - u * chw);
+    }
+  }
   if constexpr (V == 4) {
     const f32x4 xv = *reinterpret_cast<const f32x4*>(x + i), cv = *reinterpret_cast<const f32x4*>(ec + i);
     const f32x4 uv = eu ? *reinterpret_cast<const f32x4*>(eu + i) : f32x4{0.f, 0.f, 0.f, 0.f};
-    const f32x4 nv = nz ? *reinterpret_cast<const f32x4*>(nz + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+    const f32x4 nv = nz ? *reinterpret_cast<const f32x4*>(nz + ni) : f32x4{0.f, 0.f, 0.f, 0.f};
     f32x4 rv, pv;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -299,7 +309,7 @@ __global__ void ddim_kernel(const float* x, const float* __restrict__ ec, const 
     if (p0) *reinterpret_cast<f32x4*>(p0 + i) = pv;
   } else {
     float r, p;
-    ddim_elem(x[i], ec[i], eu ? eu[i] : 0.f, eu != nullptr, g, s1m, sqrt_at, sqrt_aprev, dc, sigma, nz ? nz[i] : 0.f, nz != nullptr, r, p);
+    ddim_elem(x[i], ec[i], eu ? eu[i] : 0.f, eu != nullptr, g, s1m, sqrt_at, sqrt_aprev, dc, sigma, nz ? nz[ni] : 0.f, nz != nullptr, r, p);
     xo[i] = r;
     if (p0) p0[i] = p;
   }
@@ -319,23 +329,31 @@ __device__ __forceinline__ float blend_elem(float x0, float nz, float m, float i
   return u + v;                                                                       // ddim.py:97
 }
 
-template <int V>
+// UNITS (idf_q_sample_blend_units): img / out are U work units, x0 / nz / mask one row per IMAGE; unit u reads row img_of[u] of the
+// three, the entry clamped to [0, B-1].  V == 4: CHW % 4 == 0, so a vector never crosses a unit.  !UNITS: img_of / B are unused.
+template <int V, bool UNITS>
 __global__ void q_sample_blend_kernel(const float* __restrict__ x0, const float* __restrict__ nz, const float* __restrict__ mask,
                                       const float* img, float sa, float s1, float* out, long long total, long long HW,
-                                      long long CHW, bool mask_per_channel) {
+                                      long long CHW, bool mask_per_channel, const int* __restrict__ img_of, int B) {
   static_assert(V == 1 || V == 4, "scalar or 16-B accesses");
   const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * V;
   if (i >= total) return;                                                             // V == 4: whole vectors, each inside one mask row
-  const long long mi = mask_per_channel ? i : (i / CHW) * HW + i % HW;
+  long long si = i, row = i / CHW;                                                    // the element's place in x0 / nz, its row there
+  if constexpr (UNITS) {
+    const long long r = i - row * CHW;
+    row = min(max(img_of[row], 0), B - 1);
+    si = row * CHW + r;
+  }
+  const long long mi = mask_per_channel ? si : row * HW + i % HW;
   if constexpr (V == 4) {
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(x0 + i), nv = *reinterpret_cast<const f32x4*>(nz + i);
+    const f32x4 xv = *reinterpret_cast<const f32x4*>(x0 + si), nv = *reinterpret_cast<const f32x4*>(nz + si);
     const f32x4 mv = *reinterpret_cast<const f32x4*>(mask + mi), iv = *reinterpret_cast<const f32x4*>(img + i);
     f32x4 ov;
 #pragma unroll
     for (int j = 0; j < 4; ++j) ov[j] = blend_elem(xv[j], nv[j], mv[j], iv[j], sa, s1);
     *reinterpret_cast<f32x4*>(out + i) = ov;
   } else {
-    out[i] = blend_elem(x0[i], nz[i], mask[mi], img[i], sa, s1);
+    out[i] = blend_elem(x0[si], nz[si], mask[mi], img[i], sa, s1);
   }
 }
 
@@ -633,9 +651,11 @@ extern "C" int idf_plms_update(const float* x, const float* e_t, const float* e1
   return idf_launch_status();
 }
 
-extern "C" int idf_ddim_update(const float* x, const float* eps_cond, const float* eps_uncond, float guidance, float a_t, float a_prev,
-                               float sigma_t, float sqrt_1m_at, const float* noise, float* x_prev, float* pred_x0, long long n,
-                               void* stream) {
+// The one launcher of ddim_kernel.  img_of == nullptr: n elements, the noise row is the element's own (idf_ddim_update); else
+// n = U chw elements and the noise is [B][chw], read through the table (idf_ddim_update_units).
+static int ddim_launch(const float* x, const float* eps_cond, const float* eps_uncond, float guidance, float a_t, float a_prev,
+                       float sigma_t, float sqrt_1m_at, const float* noise, float* x_prev, float* pred_x0, long long n,
+                       const int* img_of, long long chw, int B, void* stream) {
 #pragma clang fp contract(off)
   if (!x || !eps_cond || !x_prev || n < 1) return IDF_E_ARG;
   if (!(a_t > 0.0f) || !(a_prev >= 0.0f) || !(sigma_t >= 0.0f)) return IDF_E_ARG;
@@ -647,29 +667,66 @@ extern "C" int idf_ddim_update(const float* x, const float* eps_cond, const floa
   if (!(rad >= 0.0f)) return IDF_E_ARG;
   const float sqrt_at = sqrtf(a_t), sqrt_aprev = sqrtf(a_prev), dc = sqrtf(rad);
   hipStream_t s = (hipStream_t)stream;
-  const bool v4 = (n % 4) == 0 && aligned16(x) && aligned16(eps_cond) && aligned16(x_prev) && (!eps_uncond || aligned16(eps_uncond)) &&
-                  (!noise || aligned16(noise)) && (!pred_x0 || aligned16(pred_x0));
-  if (v4) hipLaunchKernelGGL(ddim_kernel<4>, grid1d(n / 4), dim3(256), 0, s, x, eps_cond, eps_uncond, guidance, sqrt_1m_at, sqrt_at,
-                             sqrt_aprev, dc, sigma_t, noise, x_prev, pred_x0, n);
-  else hipLaunchKernelGGL(ddim_kernel<1>, grid1d(n), dim3(256), 0, s, x, eps_cond, eps_uncond, guidance, sqrt_1m_at, sqrt_at,
-                          sqrt_aprev, dc, sigma_t, noise, x_prev, pred_x0, n);
+  // 16-B accesses: every pointer aligned and whole vectors (through the table: whole vectors inside every unit)
+  const bool v4 = ((img_of ? chw : n) % 4) == 0 && aligned16(x) && aligned16(eps_cond) && aligned16(x_prev) &&
+                  (!eps_uncond || aligned16(eps_uncond)) && (!noise || aligned16(noise)) && (!pred_x0 || aligned16(pred_x0));
+#define IDF_DDIM_LAUNCH(V, UNITS)                                                                                                   \
+  hipLaunchKernelGGL((ddim_kernel<V, UNITS>), grid1d(n / V), dim3(256), 0, s, x, eps_cond, eps_uncond, guidance, sqrt_1m_at, sqrt_at, \
+                     sqrt_aprev, dc, sigma_t, noise, x_prev, pred_x0, n, img_of, chw, B)
+  if (img_of) { if (v4) IDF_DDIM_LAUNCH(4, true); else IDF_DDIM_LAUNCH(1, true); }
+  else { if (v4) IDF_DDIM_LAUNCH(4, false); else IDF_DDIM_LAUNCH(1, false); }
+#undef IDF_DDIM_LAUNCH
+  return idf_launch_status();
+}
+
+extern "C" int idf_ddim_update(const float* x, const float* eps_cond, const float* eps_uncond, float guidance, float a_t, float a_prev,
+                               float sigma_t, float sqrt_1m_at, const float* noise, float* x_prev, float* pred_x0, long long n,
+                               void* stream) {
+  return ddim_launch(x, eps_cond, eps_uncond, guidance, a_t, a_prev, sigma_t, sqrt_1m_at, noise, x_prev, pred_x0, n, nullptr, 0, 0, stream);
+}
+
+extern "C" int idf_ddim_update_units(const float* x, const float* eps_cond, const float* eps_uncond, float guidance, float a_t,
+                                     float a_prev, float sigma_t, float sqrt_1m_at, const float* noise, const int* img_of,
+                                     float* x_prev, float* pred_x0, int U, int B, long long chw, void* stream) {
+  if (U < 1 || B < 1 || chw < 1) return IDF_E_ARG;
+  if (noise && !img_of && U != B) return IDF_E_ARG;              // a per-image operand needs the table (U == B: unit u is image u)
+  // without noise nothing is per image: the table is not read, the launch is idf_ddim_update's
+  return ddim_launch(x, eps_cond, eps_uncond, guidance, a_t, a_prev, sigma_t, sqrt_1m_at, noise, x_prev, pred_x0, (long long)U * chw,
+                     noise ? img_of : nullptr, chw, B, stream);
+}
+
+// The one launcher of q_sample_blend_kernel over `rows` rows of img / out.  img_of == nullptr: x0 / noise / mask have the same rows
+// (idf_q_sample_blend); else they have B rows, read through the table (idf_q_sample_blend_units).
+static int blend_launch(const float* x0, const float* noise, const float* mask, const float* img, float sqrt_ac, float sqrt_1m_ac,
+                        float* out, int rows, int C, long long HW, int mask_channels, const int* img_of, int B, void* stream) {
+  if (!x0 || !noise || !mask || !img || !out || rows < 1 || C < 1 || HW < 1) return IDF_E_ARG;
+  if (mask_channels != 1 && mask_channels != C) return IDF_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const long long CHW = (long long)C * HW, total = (long long)rows * CHW;
+  const bool per_channel = mask_channels == C;                   // C == 1: both layouts are the same tensor
+  // 16-B accesses: every pointer aligned, whole vectors (through the table: whole vectors inside every unit), and no vector across a
+  // row of a channel-broadcast mask
+  const bool v4 = ((img_of ? CHW : total) % 4) == 0 && (per_channel || (HW % 4) == 0) && aligned16(x0) && aligned16(noise) &&
+                  aligned16(mask) && aligned16(img) && aligned16(out);
+#define IDF_BLEND_LAUNCH(V, UNITS)                                                                                                  \
+  hipLaunchKernelGGL((q_sample_blend_kernel<V, UNITS>), grid1d(total / V), dim3(256), 0, s, x0, noise, mask, img, sqrt_ac, sqrt_1m_ac, \
+                     out, total, HW, CHW, per_channel, img_of, B)
+  if (img_of) { if (v4) IDF_BLEND_LAUNCH(4, true); else IDF_BLEND_LAUNCH(1, true); }
+  else { if (v4) IDF_BLEND_LAUNCH(4, false); else IDF_BLEND_LAUNCH(1, false); }
+#undef IDF_BLEND_LAUNCH
   return idf_launch_status();
 }
 
 extern "C" int idf_q_sample_blend(const float* x0, const float* noise, const float* mask, const float* img, float sqrt_ac,
                                   float sqrt_1m_ac, float* out, int B, int C, long long HW, int mask_channels, void* stream) {
-  if (!x0 || !noise || !mask || !img || !out || B < 1 || C < 1 || HW < 1) return IDF_E_ARG;
-  if (mask_channels != 1 && mask_channels != C) return IDF_E_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const long long CHW = (long long)C * HW, total = (long long)B * CHW;
-  const bool per_channel = mask_channels == C;                   // C == 1: both layouts are the same tensor
-  // 16-B accesses: every pointer aligned, whole vectors, and no vector across a row of a channel-broadcast mask
-  const bool v4 = (total % 4) == 0 && (per_channel || (HW % 4) == 0) && aligned16(x0) && aligned16(noise) && aligned16(mask) && aligned16(img) && aligned16(out);
-  if (v4) hipLaunchKernelGGL(q_sample_blend_kernel<4>, grid1d(total / 4), dim3(256), 0, s, x0, noise, mask, img, sqrt_ac, sqrt_1m_ac,
-                             out, total, HW, CHW, per_channel);
-  else hipLaunchKernelGGL(q_sample_blend_kernel<1>, grid1d(total), dim3(256), 0, s, x0, noise, mask, img, sqrt_ac, sqrt_1m_ac, out,
-                          total, HW, CHW, per_channel);
-  return idf_launch_status();
+  return blend_launch(x0, noise, mask, img, sqrt_ac, sqrt_1m_ac, out, B, C, HW, mask_channels, nullptr, B, stream);
+}
+
+extern "C" int idf_q_sample_blend_units(const float* x0, const float* noise, const float* mask, const float* img, const int* img_of,
+                                        float sqrt_ac, float sqrt_1m_ac, float* out, int U, int B, int C, long long HW,
+                                        int mask_channels, void* stream) {
+  if (!img_of || U < 1 || B < 1) return IDF_E_ARG;              // x0, noise and mask are per image: the table is always needed
+  return blend_launch(x0, noise, mask, img, sqrt_ac, sqrt_1m_ac, out, U, C, HW, mask_channels, img_of, B, stream);
 }
 
 extern "C" int idf_mis_merge(const float* lat, const int* boxes, float* out, int n_inst, int B, int C, int H, int W,

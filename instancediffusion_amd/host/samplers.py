@@ -1,4 +1,4 @@
-"""PLMS sampler, the Multi-instance Sampler (MIS) and the DDIM sampler for the MI355X engine.
+"""PLMS sampler, the Multi-instance Sampler (MIS, on PLMS and on DDIM steps) and the DDIM sampler for the MI355X engine.
 
 Host mirror of ``ldm/models/diffusion/plms.py`` (PLMSSampler), ``plms_instance.py`` (PLMSSamplerInst) and ``ddim.py``
 (DDIMSampler): same constructor / ``sample()`` API, same schedule, same update rule and quirks, different execution plan:
@@ -14,7 +14,10 @@ Host mirror of ``ldm/models/diffusion/plms.py`` (PLMSSampler), ``plms_instance.p
     same ``idf_mis_merge`` call as on one rank -- outputs are bit-identical at every world size -- and phase 2 is
     sharded over images;
   * DDIM: the raw [cond | uncond] eps halves of the step's one forward go straight into ``idf_ddim_update`` (guidance, pred_x0,
-    direction and noise term in one launch), the inpainting blend in front of a step is one ``idf_q_sample_blend`` launch.
+    direction and noise term in one launch), the inpainting blend in front of a step is one ``idf_q_sample_blend`` launch;
+  * ``DDIMSamplerInst``: the Multi-instance Sampler on DDIM steps (the reference has none).  The two Inst classes share units, bank,
+    chunking, hoist, merge and sharding and differ in one hook, ``_advance`` ("advance these n rows one step"), and in the history
+    that travels from phase 1 to phase 2 (DDIM: none).
 """
 from __future__ import annotations
 
@@ -37,6 +40,15 @@ def guided_uc_shared(uc: torch.Tensor) -> bool:
     if uc.stride(0) == 0:
         return True
     return bool((uc[1:] == uc[:1]).all())
+
+
+def ddim_sigmas(a32: np.ndarray, a_prev32: np.ndarray, eta: float) -> np.ndarray:
+    """util.py:78 as the reference's operand types evaluate it: ``alphas`` is a float32 torch tensor and ``alphas_prev`` a float64
+    numpy array, so ``(1 - alphas_prev) / (1 - alphas)`` runs as Tensor.__rtruediv__ = reciprocal(1 - alphas) in float32, times the
+    float64 numerator; every other operation is float64.  A step rounds its sigma to float32."""
+    a, ap = a32.astype(np.float64), a_prev32.astype(np.float64)
+    recip = (np.float32(1.0) / (np.float32(1.0) - a32)).astype(np.float64)
+    return eta * np.sqrt(recip * (1 - ap) * (1 - a / ap))
 
 
 class _PLMSBase(object):
@@ -220,6 +232,40 @@ class PLMSSamplerInst(_PLMSBase):
             on = False
         return (dist, dist.get_rank(), dist.get_world_size()) if on else (None, 0, 1)
 
+    # ---- the step rule: all a Multi-instance Sampler on another step (``DDIMSamplerInst``) overrides -----------------------------
+    def _begin_run(self, shape, dist=None):
+        """Called once per sampling call, after the checks and before any forward; ``shape``: the stacked latents of ALL images."""
+
+    def _hoist_input(self, x_start):
+        """What the hoisted first evaluation sees of the start latents: step 0's input, the same for every unit of an image."""
+        return x_start
+
+    def _advance(self, x, hist, i, time_range, total, pair, n, guided, guidance_scale, first=None, rows_img=None):
+        """Advance the n rows of x one step (step i of the schedule): -> the new x; ``hist`` is updated in place.  ``first``: the raw
+        (cond, uncond) eps halves of this evaluation when the caller already has them (the hoist); ``rows_img[k]``: the image row k
+        belongs to.  Here: p_sample_plms, ``hist`` = the eps history."""
+        e_first = None
+        if first is not None:
+            ops = self.engine.ops
+            e_first = ops.cfg_combine(first[0], first[1], guidance_scale, ops.empty(x.shape, torch.float32))
+        step_next = int(time_range[min(i + 1, len(time_range) - 1)])
+        x, e_t = self._plms_step(x, hist, total - i - 1, int(time_range[i]), step_next, pair, n, guided, guidance_scale, e_t_first=e_first)
+        self._push(hist, e_t)
+        return x
+
+    def _new_history(self):
+        """The history a run of rows starts with; what travels from phase 1 to phase 2 is row k's part of it, ``_history_row``,
+        re-stacked over the rows of phase 2 by ``_history_stack``."""
+        return []
+
+    @staticmethod
+    def _history_row(hist, k):
+        return [e[k] for e in hist]
+
+    @staticmethod
+    def _history_stack(rows):
+        return [torch.stack([h[i] for h in rows]) for i in range(len(rows[0]))]
+
     # ---- the two phases over a list of work units (shared by ``plms_sampling`` and ``sample_layouts``) ----------------
     # A unit is any hashable key; the caller says where its conditioning lives (``row_of[u]``: bank row), which image it
     # belongs to (``img_of(u)``: index into the stacked start latents, key of ``row_unc``) and where its start latent is (``x_of(u)``).
@@ -234,9 +280,8 @@ class PLMSSamplerInst(_PLMSBase):
                 guidance_scale, per_fwd):
         """Advance every unit of ``chunks`` through the first ``mis_step`` steps, one batched forward per chunk and evaluation.
         ``x_start`` (the start latents of all images, [n_img, 4, H, W] on the device) asks for the hoisted first evaluation, None
-        for none.  Returns ({unit: latent}, {unit: eps history})."""
+        for none.  Returns ({unit: latent}, {unit: its history, ``_history_row``})."""
         eng = self.engine
-        ops = eng.ops
         dev = eng.device
         x_units: Dict[tuple, torch.Tensor] = {}
         eps_units: Dict[tuple, list] = {}
@@ -249,6 +294,7 @@ class PLMSSamplerInst(_PLMSBase):
         E_first = None
         if x_start is not None:
             self._apply_alpha(alphas, 0)
+            x_start = self._hoist_input(x_start)
             imgs = sorted({img_of(u) for u in units})
             row_ids = [row_of[u] for u in units] + [row_unc[b] for b in imgs]
             row_img = [img_of(u) for u in units] + imgs
@@ -269,41 +315,36 @@ class PLMSSamplerInst(_PLMSBase):
             n = len(chunk)
             pair = None
             x = torch.stack([x_of(u) for u in chunk]).to(dev, torch.float32)
-            old: list = []
-            for i, step in enumerate(time_range[:mis_step]):
+            old = self._new_history()
+            rows_img = [img_of(u) for u in chunk]
+            for i in range(mis_step):
                 self._apply_alpha(alphas, i)
-                index = total - i - 1
-                step_next = int(time_range[min(i + 1, len(time_range) - 1)])
-                e_first = None
+                first = None
                 if i == 0 and E_first is not None:
                     ic = torch.tensor([first_idx[u] for u in chunk], device=dev, dtype=torch.long)
                     iu = torch.tensor([first_unc[img_of(u)] for u in chunk], device=dev, dtype=torch.long)
-                    e_first = ops.cfg_combine(E_first[ic].contiguous(), E_first[iu].contiguous(), guidance_scale,
-                                              ops.empty(x.shape, torch.float32))
+                    first = (E_first[ic].contiguous(), E_first[iu].contiguous())
                 if i == 0 or pair is None:
                     pair = eng.gather_cond(bank, self._rows(chunk, row_of, row_unc, img_of, guided))
-                x, e_t = self._plms_step(x, old, index, int(step), step_next, pair, n, guided, guidance_scale,
-                                         e_t_first=e_first)
-                self._push(old, e_t)
+                x = self._advance(x, old, i, time_range, total, pair, n, guided, guidance_scale, first=first, rows_img=rows_img)
             for k, u in enumerate(chunk):
                 x_units[u] = x[k]
-                eps_units[u] = [e[k] for e in old]
+                eps_units[u] = self._history_row(old, k)
         return x_units, eps_units
 
-    def _phase2(self, x, old, pair, n, alphas, time_range, total, mis_step, guided, guidance_scale):
-        """The shared trajectory from step ``mis_step`` on (plms_instance.py:138-156): n rows, ``old`` = their eps history."""
-        for i, step in enumerate(time_range):
-            if i < mis_step:
-                continue
+    def _phase2(self, x, old, pair, n, alphas, time_range, total, mis_step, guided, guidance_scale, rows_img):
+        """The shared trajectory from step ``mis_step`` on (plms_instance.py:138-156): n rows, ``old`` = their history."""
+        for i in range(mis_step, len(time_range)):
             self._apply_alpha(alphas, i)
-            index = total - i - 1
-            step_next = int(time_range[min(i + 1, len(time_range) - 1)])
-            x, e_t = self._plms_step(x, old, index, int(step), step_next, pair, n, guided, guidance_scale)
-            self._push(old, e_t)
+            x = self._advance(x, old, i, time_range, total, pair, n, guided, guidance_scale, rows_img=rows_img)
         return x
 
     @torch.no_grad()
     def plms_sampling(self, shape, input_all, uc=None, guidance_scale=1, mask=None, x0=None):
+        """``mask`` / ``x0`` are accepted and ignored, as in the reference (plms_instance.py never reads them)."""
+        return self._mis_sampling(shape, input_all, uc, guidance_scale)
+
+    def _mis_sampling(self, shape, input_all, uc, guidance_scale):
         eng = self.engine
         ops = eng.ops
         dev = eng.device
@@ -324,6 +365,7 @@ class PLMSSamplerInst(_PLMSBase):
         alphas = self.alpha_generator_func(len(time_range)) if self.alpha_generator_func is not None else None
         self._check_first_conv(alphas)
         mis_step = int(total * self.mis)
+        self._begin_run(tuple(shape), dist)
 
         # ---------------- work split (decided BEFORE any conditioning is built) ---------------------------------
         # Phase 1 = N+1 independent trajectories per image (plms_instance.py:86-104); work unit = (instance j, image b).  "image" sharding: owner = b % world -- every trajectory of an image lives on
@@ -449,10 +491,9 @@ class PLMSSamplerInst(_PLMSBase):
             idx = torch.tensor(mine, device=dev)
             n = len(mine)
             x = merged[idx].contiguous()
-            old = [torch.stack([eps_units[(0, b)][k] for b in mine]) for k in range(len(eps_units[(0, mine[0])]))] \
-                if mis_step > 0 else []
+            old = self._history_stack([eps_units[(0, b)] for b in mine]) if mis_step > 0 else self._new_history()
             pair = eng.gather_cond(bank, rows([(0, b) for b in mine]))
-            out[idx] = self._phase2(x, old, pair, n, alphas, time_range, total, mis_step, guided, guidance_scale)
+            out[idx] = self._phase2(x, old, pair, n, alphas, time_range, total, mis_step, guided, guidance_scale, mine)
         if dist is not None:
             # finished images of every rank, again as an all-gather of what each rank owns (images b = r, r + W, ...)
             cap = (B + world - 1) // world
@@ -538,6 +579,9 @@ class PLMSSamplerInst(_PLMSBase):
         schedule that reaches 0 inside phase 1 (the reference's serial-order quirk cannot be reproduced for independent layouts),
         ``crop_and_paste_latents`` with a layout without instances."""
         self.make_schedule(ddim_num_steps=S)
+        return self._mis_layouts(layouts, uc, guidance_scale)
+
+    def _mis_layouts(self, layouts, uc, guidance_scale):
         eng = self.engine
         ops = eng.ops
         dev = eng.device
@@ -569,6 +613,7 @@ class PLMSSamplerInst(_PLMSBase):
         n_img = sum(K)
         shape = (n_img,) + tuple(xs[0].shape[1:])
         H, W = int(shape[2]), int(shape[3])
+        self._begin_run(shape, None)
 
         # ---------------- units, instance-major as in plms_sampling (a uniform layout list forms sample()'s forwards) -------
         units = [(l, j, k) for j in range(max(n_inst) + 1) for l in range(L) if j <= n_inst[l] for k in range(K[l])]
@@ -621,9 +666,10 @@ class PLMSSamplerInst(_PLMSBase):
 
         # ---------------- phase 2: one row per image, with the eps history of that image's global unit ------------------------
         glob = [(l, 0, k) for l in range(L) for k in range(K[l])]
-        old = [torch.stack([eps_units[u][i] for u in glob]) for i in range(len(eps_units[glob[0]]))] if mis_step > 0 else []
+        old = self._history_stack([eps_units[u] for u in glob]) if mis_step > 0 else self._new_history()
         pair = eng.gather_cond(bank, self._rows(glob, row_of, row_unc, img_of, guided))
-        return self._phase2(merged.contiguous(), old, pair, n_img, alphas, time_range, total, mis_step, guided, guidance_scale)
+        return self._phase2(merged.contiguous(), old, pair, n_img, alphas, time_range, total, mis_step, guided, guidance_scale,
+                            list(range(n_img)))
 
 
 class DDIMSampler(_PLMSBase):
@@ -641,12 +687,7 @@ class DDIMSampler(_PLMSBase):
     # ---- schedule (ddim.py:25-54; util.py:55-83) ------------------------------------------------------------
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.):
         super().make_schedule(ddim_num_steps, ddim_discretize, 0.)             # timesteps, a_t, a_prev, sqrt(1 - a_t): float32
-        # util.py:78 as the reference's operand types evaluate it: ``alphas`` is a float32 torch tensor and ``alphas_prev`` a
-        # float64 numpy array, so ``(1 - alphas_prev) / (1 - alphas)`` runs as Tensor.__rtruediv__ = reciprocal(1 - alphas) in
-        # float32, times the float64 numerator; every other operation is float64.  A step rounds its sigma to float32.
-        a32, a, ap = self.ddim_alphas, self.ddim_alphas.astype(np.float64), self.ddim_alphas_prev.astype(np.float64)
-        recip = (np.float32(1.0) / (np.float32(1.0) - a32)).astype(np.float64)
-        self.ddim_sigmas = ddim_eta * np.sqrt(recip * (1 - ap) * (1 - a / ap))
+        self.ddim_sigmas = ddim_sigmas(self.ddim_alphas, self.ddim_alphas_prev, ddim_eta)
 
     @torch.no_grad()
     def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, eta=0.):
@@ -705,3 +746,176 @@ class DDIMSampler(_PLMSBase):
                                   sigma, float(self.ddim_sqrt_one_minus_alphas[index]), noise, ops.empty(img.shape, torch.float32))
             input["x"] = img
         return img
+
+
+class DDIMSamplerInst(PLMSSamplerInst):
+    """The Multi-instance Sampler on DDIM steps: ``PLMSSamplerInst``'s units, conditioning bank, chunking, hoisted first evaluation,
+    merge and sharding, with ``DDIMSampler``'s step -- eta > 0 and the ``mask`` / ``x0`` inpainting blend included -- in both phases.
+    The reference has no such sampler; phase 1 follows plms_instance.py:86-104 with ddim.py:94-131 as the step, phase 2 is ddim.py.
+
+    A DDIM step carries no history: nothing but the latents travels from phase 1 to phase 2, and a step is ONE forward.
+
+    Noise: every draw comes from ``noise_fn`` (as in ``DDIMSampler``) and is one draw per IMAGE per step, [n_img, 4, H, W], shared by
+    the image's N+1 trajectories (they start from the same latent; independent noise would decorrelate what the merge averages).
+    Order within a step: the q_sample draw when inpainting, then the step's draw when sigma != 0.  Phase 1 runs chunk-major, so all
+    draws of a call are made up front, in step order: the result does not depend on ``max_units`` / chunking, nor on the world size
+    (every rank draws, rank 0's draws are broadcast, as the start noise is).  Per-image operands are never gathered per unit: the
+    unit kernels (``idf_ddim_update_units``, ``idf_q_sample_blend_units``) read them through a device table unit -> image."""
+
+    def __init__(self, diffusion, model, schedule="linear", alpha_generator_func=None, set_alpha_scale=None, mis=0.0,
+                 crop_and_paste_latents=False, shard_across_ranks: Optional[bool] = None, max_units: int = 128,
+                 unit_sharding: str = "auto"):
+        super().__init__(diffusion, model, schedule, alpha_generator_func, set_alpha_scale, mis, crop_and_paste_latents,
+                         shard_across_ranks, max_units, unit_sharding)
+        self.noise_fn = lambda shape: torch.randn(tuple(shape), device=self.engine.device, dtype=torch.float32)
+        self._inpaint = None            # (x0, mask) of the call being set up, one row per image
+        self._run = None                # per-call state of the step hook, see _begin_run
+
+    def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.):
+        super().make_schedule(ddim_num_steps, ddim_discretize, 0.)
+        self.ddim_sigmas = ddim_sigmas(self.ddim_alphas, self.ddim_alphas_prev, ddim_eta)
+
+    @torch.no_grad()
+    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, eta=0.):
+        self.make_schedule(ddim_num_steps=S, ddim_eta=eta)
+        self._inpaint = None
+        if mask is not None:
+            assert x0 is not None
+            self._inpaint = (x0, mask)
+        try:
+            return self._mis_sampling(shape, self._without_idle_instances(input), uc, guidance_scale)
+        finally:
+            self._inpaint = self._run = None        # the draws, x0 / mask and the tables live for the call only
+
+    def plms_sampling(self, *args, **kwargs):
+        raise NotImplementedError("DDIMSamplerInst runs DDIM steps: use sample() or sample_layouts()")
+
+    @torch.no_grad()
+    def sample_layouts(self, S, layouts, uc=None, guidance_scale=1, eta=0., masks=None, x0s=None):
+        """``PLMSSamplerInst.sample_layouts`` on DDIM steps.  ``masks`` / ``x0s``: None, or one entry per layout -- a mask [1 or K_l, 1 or
+        4, H, W] and an x0 [1 or K_l, 4, H, W], or None for a layout that is not inpainted (it gets an all-zero mask, which leaves its
+        latents bit for bit as they are; the q_sample draw still covers its images)."""
+        self.make_schedule(ddim_num_steps=S, ddim_eta=eta)
+        self._inpaint = None
+        if masks is None and x0s is not None and any(x is not None for x in x0s):
+            raise ValueError("sample_layouts: x0s without masks; masks and x0s hold one entry per layout, both given or both None")
+        if masks is not None and any(m is not None for m in masks):
+            if x0s is None or len(masks) != len(layouts) or len(x0s) != len(layouts) or \
+                    any((m is None) != (x is None) for m, x in zip(masks, x0s)):
+                raise ValueError("sample_layouts: masks and x0s hold one entry per layout, both given or both None")
+            ms, xs = [], []
+            per_channel = any(m is not None and m.shape[1] != 1 for m in masks)
+            for lay, m, x in zip(layouts, masks, x0s):
+                lat = lay[0]["x"]
+                K, Cc = int(lat.shape[0]), int(lat.shape[1])
+                if m is None:
+                    m, x = lat.new_zeros((1, 1) + tuple(lat.shape[2:])), torch.zeros_like(lat[:1])
+                ms.append(m.expand(K, Cc if per_channel else 1, *lat.shape[2:]))
+                xs.append(x.expand(K, *lat.shape[1:]))
+            self._inpaint = (torch.cat([x.to(self.engine.device) for x in xs], 0), torch.cat([m.to(self.engine.device) for m in ms], 0))
+        try:
+            return self._mis_layouts([self._without_idle_instances(lay) for lay in layouts], uc, guidance_scale)
+        finally:
+            self._inpaint = self._run = None
+
+    def _without_idle_instances(self, input_all):
+        """With no phase-1 step (``int(S * mis) == 0``) the instance trajectories are never advanced and the mean merges N+1 copies
+        of the start latent -- (x + x + x) / 3 is not x in fp32.  Only the global input is kept then: the mean of one unit is exact,
+        so the call IS ``DDIMSampler`` on the global input, bit for bit.  (Crop-and-paste copies values; it keeps its boxes.)"""
+        if int(self.ddim_timesteps.shape[0] * self.mis) == 0 and not self.crop_and_paste_latents:
+            return input_all[:1]
+        return input_all
+
+    # ---- the step rule ------------------------------------------------------------------------------------------------------
+    def _begin_run(self, shape, dist=None):
+        """All noise of the call, in step order, and the inpainting operands, one row per image."""
+        dev = self.engine.device
+        n_img = shape[0]
+        total = self.ddim_timesteps.shape[0]
+        run = dict(n_img=n_img, tables={}, q_noise=[None] * total, step_noise=[None] * total, x0=None)
+        if self._inpaint is not None:
+            x0, mask = self._inpaint
+            run["x0"] = x0.to(dev, torch.float32).expand(shape).contiguous()
+            mask = mask.to(dev, torch.float32)
+            run["mask"] = mask.expand(n_img, mask.shape[1] if mask.shape[1] == shape[1] else 1, *shape[2:]).contiguous()
+            run["sqrt_ac"] = self.diffusion.sqrt_alphas_cumprod.detach().to(torch.float32).cpu()
+            run["sqrt_1m_ac"] = self.diffusion.sqrt_one_minus_alphas_cumprod.detach().to(torch.float32).cpu()
+
+        def draw():
+            n = self.noise_fn(shape).to(dev, torch.float32).contiguous()
+            if dist is not None:
+                dist.broadcast(n, 0)
+            return n
+        for i in range(total):
+            if run["x0"] is not None:
+                run["q_noise"][i] = draw()
+            if float(np.float32(self.ddim_sigmas[total - i - 1])) != 0:
+                run["step_noise"][i] = draw()
+        self._run = run
+        self._inpaint = None
+
+    def _table(self, rows_img):
+        """Device int32 table row -> image of the unit kernels; None when the rows ARE the images, in order."""
+        run = self._run
+        if list(rows_img) == list(range(run["n_img"])):
+            return None
+        key = tuple(rows_img)
+        if key not in run["tables"]:
+            run["tables"][key] = torch.tensor(key, dtype=torch.int32).to(self.engine.device)
+        return run["tables"][key]
+
+    def _blend(self, x, i, step, tab):
+        """ddim.py:94-98 in front of step i: one launch for all rows."""
+        run, ops = self._run, self.engine.ops
+        sa, s1 = float(run["sqrt_ac"][step]), float(run["sqrt_1m_ac"][step])
+        out = ops.empty(x.shape, torch.float32)
+        if tab is None:
+            return ops.q_sample_blend(run["x0"], run["q_noise"][i], run["mask"], x, sa, s1, out)
+        return ops.q_sample_blend_units(run["x0"], run["q_noise"][i], run["mask"], x, tab, sa, s1, out)
+
+    def _hoist_input(self, x_start):
+        # the blend is per image, so an image's trajectories still share step 0's input; every chunk blends its own rows again, to
+        # the same values
+        if self._run["x0"] is None:
+            return x_start
+        return self._blend(x_start.contiguous(), 0, int(np.flip(self.ddim_timesteps)[0]), None)
+
+    def _advance(self, x, hist, i, time_range, total, pair, n, guided, guidance_scale, first=None, rows_img=None):
+        """The blend (when inpainting) and p_sample_ddim (ddim.py:107-131): one batched [cond | uncond] forward, its raw halves into
+        the fused update."""
+        eng = self.engine
+        ops = eng.ops
+        run = self._run
+        step, index = int(time_range[i]), total - i - 1
+        tab = self._table(rows_img)
+        x = x.contiguous()
+        if run["x0"] is not None:
+            x = self._blend(x, i, step, tab)
+        if first is not None:
+            e_c, e_u = first
+        else:
+            t = torch.full((n,), float(step), device=x.device, dtype=torch.float32)
+            if guided:
+                e2 = eng.forward_cond(x, t, pair, out=eng.buf("smp.eps2", (2 * n,) + tuple(x.shape[1:]), torch.float32), paired=True)
+                e_c, e_u = e2[:n], e2[n:]
+            else:
+                e_c, e_u = eng.forward_cond(x, t, pair), None
+        sigma = float(np.float32(self.ddim_sigmas[index]))
+        noise = run["step_noise"][i] if sigma != 0 else None
+        args = (guidance_scale, float(self.ddim_alphas[index]), float(self.ddim_alphas_prev[index]), sigma,
+                float(self.ddim_sqrt_one_minus_alphas[index]), noise)
+        out = ops.empty(x.shape, torch.float32)
+        if tab is None:
+            return ops.ddim_update(x, e_c, e_u, *args, out)
+        return ops.ddim_update_units(x, e_c, e_u, *args, tab, out)
+
+    def _new_history(self):
+        return None
+
+    @staticmethod
+    def _history_row(hist, k):
+        return None
+
+    @staticmethod
+    def _history_stack(rows):
+        return None

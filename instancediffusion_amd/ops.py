@@ -554,6 +554,41 @@ class HipOps:
                                                B, Cc, HW, int(mask.shape[1]), self._stream()), "idf_q_sample_blend")
         return out
 
+    def ddim_update_units(self, x, e_cond, e_uncond, guidance, a_t, a_prev, sigma_t, sqrt_1m_at, noise, img_of, out, pred_x0=None):
+        """``ddim_update`` over U work units whose step noise is one row per IMAGE: x / e_cond / e_uncond / out [U,C,H,W], noise
+        [B,C,H,W] or None (needs sigma_t == 0), img_of: int32 [U] on the device (unit u reads noise[img_of[u]]; the kernel clamps the
+        entries) or None when there is no noise or U == B.  ``out`` may be ``x``."""
+        U = out.shape[0]
+        chw = out.numel() // U
+        for t in (x, e_cond, out) + tuple(t for t in (e_uncond, pred_x0) if t is not None):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == out.numel()
+        B = U
+        if noise is not None:
+            B = noise.shape[0]
+            assert noise.dtype == torch.float32 and noise.is_contiguous() and noise.numel() == B * chw
+        if img_of is not None:
+            assert img_of.dtype == torch.int32 and img_of.is_contiguous() and img_of.numel() == U and img_of.device == out.device
+        _lib.check(self.lib.idf_ddim_update_units(_p(x), _p(e_cond), _p(e_uncond), float(guidance), float(a_t), float(a_prev),
+                                                  float(sigma_t), float(sqrt_1m_at), _p(noise), _p(img_of), _p(out), _p(pred_x0), U, B,
+                                                  chw, self._stream()), "idf_ddim_update_units")
+        return out
+
+    def q_sample_blend_units(self, x0, noise, mask, img, img_of, sqrt_ac, sqrt_1m_ac, out):
+        """``q_sample_blend`` over U work units: img / out [U,C,H,W]; x0 / noise [B,C,H,W] and mask [B,1,H,W] or [B,C,H,W] one row per
+        IMAGE, unit u reads row img_of[u] (int32 [U] on the device; the kernel clamps the entries).  ``out`` may be ``img``."""
+        U, Cc = out.shape[0], out.shape[1]
+        B = x0.shape[0]
+        HW = out.numel() // (U * Cc)
+        assert img.shape == out.shape and noise.shape == x0.shape and tuple(x0.shape[1:]) == tuple(out.shape[1:])
+        assert mask.dim() == out.dim() and mask.shape[0] == B and mask.shape[1] in (1, Cc) and mask.shape[2:] == out.shape[2:]
+        for t in (x0, noise, mask, img, out):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        assert img_of.dtype == torch.int32 and img_of.is_contiguous() and img_of.numel() == U and img_of.device == out.device
+        _lib.check(self.lib.idf_q_sample_blend_units(_p(x0), _p(noise), _p(mask), _p(img), _p(img_of), float(sqrt_ac), float(sqrt_1m_ac),
+                                                     _p(out), U, B, Cc, HW, int(mask.shape[1]), self._stream()),
+                   "idf_q_sample_blend_units")
+        return out
+
     def mis_merge(self, lat, boxes_i32, out, mode):
         n1, B, Cc, H, W_ = lat.shape
         assert lat.is_contiguous() and out.is_contiguous()
