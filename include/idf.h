@@ -378,6 +378,22 @@ int idf_q_sample_blend_units(const float* x0, const float* noise, const float* m
                              float sqrt_ac, float sqrt_1m_ac, float* out, int U, int B, int C, long long HW,
                              int mask_channels /* 1 or C */, void* stream);
 
+/* ---- DPM-Solver++(2M) step (Lu et al. 2022, "DPM-Solver++", Algorithm 2, data-prediction form) behind the UNet forward -------------
+ * Added within ABI 5: a new symbol only.  The host computes the three step coefficients in float64 and rounds them to fp32 once
+ * (host/samplers.dpmpp_coeffs); per element, every operation rounded to fp32 on its own (nothing contracted, correctly rounded division):
+ *   e      = eps_uncond + guidance * (eps_cond - eps_uncond)            (eps_uncond == NULL: e = eps_cond, guidance unused)
+ *   x0_out = (x - sqrt_1m_at * e) / sqrt_at                             the data prediction: the next step's x0_last
+ *   x_prev = c_x * x + c_0 * x0_out  [+ c_1 * x0_last when x0_last != NULL: order 2]
+ * Nothing in the step is per image, so there is no units variant.  16-B accesses where every pointer is 16-B aligned and n % 4 == 0,
+ * scalar accesses otherwise (decided per launch); no LDS, no scratch, no allocation, no synchronisation; hipGraph-capturable.
+ * x_prev may alias x, x0_out may alias x0_last (a thread reads its own elements before it writes them).  IDF_E_ARG before any
+ * launch: a null x / eps_cond / x_prev / x0_out, n < 1, sqrt_at <= 0, a non-finite sqrt_at / sqrt_1m_at / c_x / c_0, a non-finite
+ * c_1 with x0_last != NULL. */
+int idf_dpmpp_update(const float* x, const float* eps_cond, const float* eps_uncond /* NULL = unguided */, float guidance,
+                     float sqrt_at, float sqrt_1m_at, float c_x, float c_0, float c_1,
+                     const float* x0_last /* NULL = order 1; then c_1 is not used */,
+                     float* x_prev, float* x0_out /* required: the next step's history */, long long n, void* stream);
+
 /* ---- Multi-instance Sampler merge (plms_instance.py:112-135) ---------------------------------------------
  * lat: [n_inst+1][B][C][H][W] fp32.  mode 0: mean over the first dim; mode 1: crop-and-paste of instance j's
  * latent box (boxes: int32 [n_inst][4] = int(box*latent_size), reference index order dim2<-x, dim3<-y).      */

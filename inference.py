@@ -10,7 +10,9 @@ Beyond the reference's flags: ``--sampler ddim`` (+ ``--ddim_eta``) runs ``DDIMS
 ``PLMSSampler``, and ``--init_image`` / ``--inpaint_mask`` reach the samplers' ``mask`` / ``x0`` arguments (plms.py:99-104,
 ddim.py:94-98): the image is encoded by ``AutoencoderKL.encode``, the mask is pooled to the latent grid.  ``--sampler ddim_inst`` runs
 ``DDIMSamplerInst``, the Multi-instance Sampler (``--mis`` > 0) on DDIM steps: ``--ddim_eta`` and inpainting work under it, with one or
-several ``--input_json`` (the one image / mask pair then applies to every layout).
+several ``--input_json`` (the one image / mask pair then applies to every layout).  ``--sampler dpmpp`` (``--mis 0``) and ``dpmpp_inst``
+(``--mis`` > 0) run DPM-Solver++(2M) -- ``DPMSolverSampler`` / ``DPMSolverSamplerInst``, ``--dpm_order``, ``--dpm_spacing`` -- meant for
+20-25 ``--steps``; inpainting and several ``--input_json`` work under both, ``--ddim_eta`` under neither.
 
 Two neighbours of the path need assets that do not exist offline; both are handled explicitly, never silently:
   * text encoding (CLIP-L/14: ``ldm/modules/encoders``, ``utils/model.py:12-18``): with ``--ckpt`` the checkpoint's
@@ -37,7 +39,8 @@ import torch
 from instancediffusion_amd.host.alpha import alpha_generator, set_alpha_scale
 from instancediffusion_amd.host.config import instantiate_from_config, load_yaml
 from instancediffusion_amd.host.input import meta_from_demo_json, prepare_batch, prepare_instance_meta, prepare_layout_inputs
-from instancediffusion_amd.host.samplers import DDIMSampler, DDIMSamplerInst, PLMSSampler, PLMSSamplerInst
+from instancediffusion_amd.host.samplers import (DDIMSampler, DDIMSamplerInst, DPMSolverSampler, DPMSolverSamplerInst, PLMSSampler,
+                                                  PLMSSamplerInst)
 
 MAX_OBJS = 30
 
@@ -206,6 +209,12 @@ def run_layouts(args, paths, model, autoencoder, diffusion, gi, text_encoder, ph
             inpaint = load_inpaint(args, model, autoencoder, dev)
             if inpaint is not None:                                        # the one image / mask pair applies to every layout
                 extra.update(masks=[inpaint[0]] * len(paths), x0s=[inpaint[1]] * len(paths))
+        elif args.sampler == "dpmpp_inst":
+            sampler = DPMSolverSamplerInst(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale, mis=args.mis)
+            extra.update(order=args.dpm_order, discretize=args.dpm_spacing)
+            inpaint = load_inpaint(args, model, autoencoder, dev)
+            if inpaint is not None:
+                extra.update(masks=[inpaint[0]] * len(paths), x0s=[inpaint[1]] * len(paths))
         else:
             sampler = PLMSSamplerInst(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale, mis=args.mis)
         layouts = prepare_layout_inputs(metas, noises, gi, text_encoder, phrase_encoder, instances=True, max_objs=MAX_OBJS, device=dev,
@@ -224,6 +233,12 @@ def run_layouts(args, paths, model, autoencoder, diffusion, gi, text_encoder, ph
         if args.sampler == "ddim":
             sampler = DDIMSampler(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale)
             extra["eta"] = args.ddim_eta or 0.
+        elif args.sampler == "dpmpp":
+            sampler = DPMSolverSampler(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale)
+            extra.update(order=args.dpm_order, discretize=args.dpm_spacing)
+            inpaint = load_inpaint(args, model, autoencoder, dev)
+            if inpaint is not None:                                        # the one image / mask pair applies to every row
+                extra.update(mask=inpaint[0].expand(n, -1, -1, -1), x0=inpaint[1].expand(n, -1, -1, -1))
         else:
             sampler = PLMSSampler(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale)
         samples = sampler.sample(S=args.steps, shape=(n, model.in_channels, model.image_size, model.image_size), input=inp,
@@ -290,9 +305,15 @@ def main():
                          "and no path, a key-seeded synthetic CLIP model")
     ap.add_argument("--keep_best", type=int, default=None,
                     help="write only the K images with the best mean CLIP score (needs --clip_score; the JSON still lists all)")
-    ap.add_argument("--sampler", choices=["plms", "ddim", "ddim_inst"], default="plms",
+    ap.add_argument("--sampler", choices=["plms", "ddim", "ddim_inst", "dpmpp", "dpmpp_inst"], default="plms",
                     help="ddim: DDIMSampler (ldm/models/diffusion/ddim.py) instead of PLMSSampler; without the Multi-instance Sampler.  "
-                         "ddim_inst: DDIMSamplerInst, the Multi-instance Sampler (--mis > 0) on DDIM steps")
+                         "ddim_inst: DDIMSamplerInst, the Multi-instance Sampler (--mis > 0) on DDIM steps.  dpmpp: DPMSolverSampler, "
+                         "DPM-Solver++(2M), usable at 20-25 --steps (--mis 0); dpmpp_inst: DPMSolverSamplerInst, the same under the "
+                         "Multi-instance Sampler (--mis > 0)")
+    ap.add_argument("--dpm_order", type=int, choices=[1, 2], default=2,
+                    help="--sampler dpmpp / dpmpp_inst: 2 = DPM-Solver++(2M), 1 = its first-order step (DDIM with eta 0)")
+    ap.add_argument("--dpm_spacing", choices=["uniform", "logsnr"], default="uniform",
+                    help="--sampler dpmpp / dpmpp_inst: uniform = the timesteps of PLMS and DDIM; logsnr = evenly spaced in log(alpha / sigma)")
     ap.add_argument("--ddim_eta", type=float, default=None,
                     help="--sampler ddim / ddim_inst: eta of the DDIM variance schedule (default 0: deterministic; 1: DDPM-like)")
     ap.add_argument("--init_image", type=str, default=None,
@@ -302,10 +323,20 @@ def main():
     args = ap.parse_args()
     paths = list(args.input_json)
     ddim_inst = args.sampler == "ddim_inst"
+    dpm = args.sampler in ("dpmpp", "dpmpp_inst")
+    inst_inpaints = args.sampler in ("ddim_inst", "dpmpp_inst")            # the Multi-instance Samplers that take mask / x0
     if ddim_inst and not args.mis > 0:
         raise SystemExit("--sampler ddim_inst is the Multi-instance Sampler on DDIM steps: give --mis > 0 (or --sampler ddim)")
+    if args.sampler == "dpmpp_inst" and not args.mis > 0:
+        raise SystemExit("--sampler dpmpp_inst is the Multi-instance Sampler on DPM-Solver++ steps: give --mis > 0 (or --sampler dpmpp)")
+    if args.sampler == "dpmpp" and args.mis > 0:
+        raise SystemExit("--sampler dpmpp runs without the Multi-instance Sampler: give --mis 0 (or --sampler dpmpp_inst)")
+    if dpm and args.ddim_eta is not None:
+        raise SystemExit("--ddim_eta: DPM-Solver++ steps are deterministic, --sampler dpmpp / dpmpp_inst take no eta")
+    if not dpm and (args.dpm_order != 2 or args.dpm_spacing != "uniform"):
+        raise SystemExit("--dpm_order / --dpm_spacing need --sampler dpmpp or dpmpp_inst")
     if len(paths) > 1:
-        if (args.init_image is not None or args.inpaint_mask is not None) and not ddim_inst:
+        if (args.init_image is not None or args.inpaint_mask is not None) and not (inst_inpaints or args.sampler == "dpmpp"):
             raise SystemExit("inpainting (--init_image / --inpaint_mask) takes one --input_json")
         if args.use_masked_att:
             raise SystemExit("--use_masked_att takes one --input_json: the mask / no-mask decision is per layout call")
@@ -319,7 +350,7 @@ def main():
         raise SystemExit("--ddim_eta must be >= 0")
     if (args.init_image is None) != (args.inpaint_mask is None):
         raise SystemExit("inpainting needs both --init_image and --inpaint_mask")
-    if args.init_image is not None and args.mis > 0 and not ddim_inst:
+    if args.init_image is not None and args.mis > 0 and not inst_inpaints:
         raise SystemExit("inpainting (--init_image / --inpaint_mask) runs without the Multi-instance Sampler: give --mis 0")
     if args.keep_best is not None and (args.clip_score is None or args.keep_best < 1):
         raise SystemExit("--keep_best K needs --clip_score and K >= 1")
@@ -397,6 +428,9 @@ def main():
         if ddim_inst:
             sampler = DDIMSamplerInst(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale, mis=args.mis)
             extra = dict(inpaint, eta=args.ddim_eta or 0.)
+        elif args.sampler == "dpmpp_inst":
+            sampler = DPMSolverSamplerInst(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale, mis=args.mis)
+            extra = dict(inpaint, order=args.dpm_order, discretize=args.dpm_spacing)
         else:
             sampler = PLMSSamplerInst(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale, mis=args.mis)
         inputs = [inp]
@@ -410,6 +444,9 @@ def main():
         if args.sampler == "ddim":
             sampler = DDIMSampler(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale)
             inpaint["eta"] = args.ddim_eta or 0.
+        elif args.sampler == "dpmpp":
+            sampler = DPMSolverSampler(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale)
+            inpaint.update(order=args.dpm_order, discretize=args.dpm_spacing)
         else:
             sampler = PLMSSampler(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale)
         samples = sampler.sample(S=args.steps, shape=shape, input=inp, uc=uc, guidance_scale=args.guidance_scale, **inpaint)

@@ -1,5 +1,6 @@
 // misc.hip -- small latency-bound kernels of the sampling path (gfx950): timestep embedding, UniFusion token-MLP
-// input builder, first conv from the fp32 NCHW latent, fused CFG / PLMS update, fused DDIM step and q_sample blend,
+// input builder, first conv from the fp32 NCHW latent, fused CFG / PLMS update, fused DDIM step and q_sample blend, fused
+// DPM-Solver++(2M) step,
 // Multi-instance-Sampler merge.
 #include "common.h"
 
@@ -312,6 +313,51 @@ __global__ void ddim_kernel(const float* x, const float* __restrict__ ec, const 
     ddim_elem(x[i], ec[i], eu ? eu[i] : 0.f, eu != nullptr, g, s1m, sqrt_at, sqrt_aprev, dc, sigma, nz ? nz[ni] : 0.f, nz != nullptr, r, p);
     xo[i] = r;
     if (p0) p0[i] = p;
+  }
+}
+
+// DPM-Solver++(2M), data-prediction form (Lu et al. 2022, Algorithm 2), behind the forward in one launch: guidance, the x0 prediction
+// p (stored: the next step's history) and x_prev = c_x x + c_0 p [+ c_1 p_last].  The three coefficients come from the host
+// (host/samplers.dpmpp_coeffs).  Every operation is rounded to fp32 on its own, as in ddim_elem.
+__device__ __forceinline__ void dpmpp_elem(float x, float ec, float eu, bool guided, float g, float s1m, float sqrt_at, float c_x,
+                                           float c_0, float c_1, float pl, bool second, float& r, float& p) {
+#pragma clang fp contract(off)
+  float e = ec;
+  if (guided) { const float d = ec - eu; const float m = g * d; e = eu + m; }
+  const float t = s1m * e;
+  p = (x - t) / sqrt_at;
+  const float a = c_x * x;
+  const float b = c_0 * p;
+  r = a + b;
+  if (second) { const float c = c_1 * pl; r = r + c; }
+}
+
+// xo may alias x and p0 may alias pl (no __restrict__ on the four): a thread reads its own elements before it writes them.
+// pl == nullptr: order 1.
+template <int V>
+__global__ void dpmpp_kernel(const float* x, const float* __restrict__ ec, const float* __restrict__ eu, float g, float s1m,
+                             float sqrt_at, float c_x, float c_0, float c_1, const float* pl, float* xo, float* p0, long long n) {
+  static_assert(V == 1 || V == 4, "scalar or 16-B accesses");
+  const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= n) return;                                                                 // V == 4: the launcher guarantees n % 4 == 0
+  if constexpr (V == 4) {
+    const f32x4 xv = *reinterpret_cast<const f32x4*>(x + i), cv = *reinterpret_cast<const f32x4*>(ec + i);
+    const f32x4 uv = eu ? *reinterpret_cast<const f32x4*>(eu + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+    const f32x4 lv = pl ? *reinterpret_cast<const f32x4*>(pl + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 rv, pv;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float r, p;
+      dpmpp_elem(xv[j], cv[j], uv[j], eu != nullptr, g, s1m, sqrt_at, c_x, c_0, c_1, lv[j], pl != nullptr, r, p);
+      rv[j] = r; pv[j] = p;
+    }
+    *reinterpret_cast<f32x4*>(xo + i) = rv;
+    *reinterpret_cast<f32x4*>(p0 + i) = pv;
+  } else {
+    float r, p;
+    dpmpp_elem(x[i], ec[i], eu ? eu[i] : 0.f, eu != nullptr, g, s1m, sqrt_at, c_x, c_0, c_1, pl ? pl[i] : 0.f, pl != nullptr, r, p);
+    xo[i] = r;
+    p0[i] = p;
   }
 }
 
@@ -693,6 +739,23 @@ extern "C" int idf_ddim_update_units(const float* x, const float* eps_cond, cons
   // without noise nothing is per image: the table is not read, the launch is idf_ddim_update's
   return ddim_launch(x, eps_cond, eps_uncond, guidance, a_t, a_prev, sigma_t, sqrt_1m_at, noise, x_prev, pred_x0, (long long)U * chw,
                      noise ? img_of : nullptr, chw, B, stream);
+}
+
+extern "C" int idf_dpmpp_update(const float* x, const float* eps_cond, const float* eps_uncond, float guidance, float sqrt_at,
+                                float sqrt_1m_at, float c_x, float c_0, float c_1, const float* x0_last, float* x_prev, float* x0_out,
+                                long long n, void* stream) {
+  if (!x || !eps_cond || !x_prev || !x0_out || n < 1) return IDF_E_ARG;
+  if (!(sqrt_at > 0.0f) || !__builtin_isfinite(sqrt_at) || !__builtin_isfinite(sqrt_1m_at) || !__builtin_isfinite(c_x) || !__builtin_isfinite(c_0)) return IDF_E_ARG;
+  if (x0_last && !__builtin_isfinite(c_1)) return IDF_E_ARG;         // order 1 does not read c_1
+  hipStream_t s = (hipStream_t)stream;
+  // 16-B accesses: every pointer aligned and whole vectors (the policy of idf_ddim_update)
+  const bool v4 = (n % 4) == 0 && aligned16(x) && aligned16(eps_cond) && aligned16(x_prev) && aligned16(x0_out) &&
+                  (!eps_uncond || aligned16(eps_uncond)) && (!x0_last || aligned16(x0_last));
+  if (v4) hipLaunchKernelGGL(dpmpp_kernel<4>, grid1d(n / 4), dim3(256), 0, s, x, eps_cond, eps_uncond, guidance, sqrt_1m_at, sqrt_at, c_x,
+                             c_0, c_1, x0_last, x_prev, x0_out, n);
+  else hipLaunchKernelGGL(dpmpp_kernel<1>, grid1d(n), dim3(256), 0, s, x, eps_cond, eps_uncond, guidance, sqrt_1m_at, sqrt_at, c_x, c_0,
+                          c_1, x0_last, x_prev, x0_out, n);
+  return idf_launch_status();
 }
 
 // The one launcher of q_sample_blend_kernel over `rows` rows of img / out.  img_of == nullptr: x0 / noise / mask have the same rows

@@ -17,7 +17,9 @@ Host mirror of ``ldm/models/diffusion/plms.py`` (PLMSSampler), ``plms_instance.p
     direction and noise term in one launch), the inpainting blend in front of a step is one ``idf_q_sample_blend`` launch;
   * ``DDIMSamplerInst``: the Multi-instance Sampler on DDIM steps (the reference has none).  The two Inst classes share units, bank,
     chunking, hoist, merge and sharding and differ in one hook, ``_advance`` ("advance these n rows one step"), and in the history
-    that travels from phase 1 to phase 2 (DDIM: none).
+    that travels from phase 1 to phase 2 (DDIM: none);
+  * ``DPMSolverSampler`` / ``DPMSolverSamplerInst``: DPM-Solver++(2M) (the reference has none) on DDIM's loop and on the Multi-instance
+    Sampler: one forward and one ``idf_dpmpp_update`` launch per step, coefficients from ``dpmpp_coeffs``, history = the last x0.
 """
 from __future__ import annotations
 
@@ -51,6 +53,55 @@ def ddim_sigmas(a32: np.ndarray, a_prev32: np.ndarray, eta: float) -> np.ndarray
     return eta * np.sqrt(recip * (1 - ap) * (1 - a / ap))
 
 
+def dpmpp_coeffs64(a_t, a_prev, a_last=None):
+    """``dpmpp_coeffs`` in front of its one rounding: three float64 values (the inputs are taken as they come)."""
+    def parts(a):
+        a = np.float64(a)
+        al, sg = np.sqrt(a), np.sqrt(1.0 - a)
+        return al, sg, np.log(al / sg)
+    _, s_t, l_t = parts(a_t)
+    al_p, s_p, l_p = parts(a_prev)
+    h = l_p - l_t
+    bc = al_p * (1.0 - np.exp(-h))
+    c_x, c_0, c_1 = s_p / s_t, bc, np.float64(0.0)
+    if a_last is not None:
+        r = (l_t - parts(a_last)[2]) / h
+        c_0, c_1 = bc * (1.0 + 1.0 / (2.0 * r)), -bc / (2.0 * r)
+    return c_x, c_0, c_1
+
+
+def dpmpp_coeffs(a_t, a_prev, a_last=None):
+    """The coefficients of one DPM-Solver++(2M) step in data-prediction form (Lu et al. 2022, "DPM-Solver++", Algorithm 2):
+    ``x_prev = c_x x + c_0 x0_t + c_1 x0_last`` with ``x0_t = (x - sigma_t e) / alpha_t`` -> (c_x, c_0, c_1) as float32.
+
+    alpha = sqrt(a), sigma = sqrt(1 - a), lambda = log(alpha / sigma), h = lambda_prev - lambda_t, Bc = alpha_prev (1 - exp(-h)).
+    ``a_last`` None (the first step of a run): order 1, (sigma_prev / sigma_t, Bc, 0) -- DDIM with eta 0.  ``a_last`` = a of the
+    previous step: order 2 with r = (lambda_t - lambda_last) / h, (sigma_prev / sigma_t, Bc (1 + 1 / (2 r)), -Bc / (2 r)).
+    The inputs are the float32 schedule values the samplers hold; everything is float64, the results are rounded once."""
+    f = [np.float32(a) for a in (a_t, a_prev)] + [None if a_last is None else np.float32(a_last)]
+    return tuple(np.float32(c) for c in dpmpp_coeffs64(*f))
+
+
+def logsnr_timesteps(S: int, alphas_cumprod) -> np.ndarray:
+    """S ascending timesteps in [1, T-1], as evenly spaced in lambda = log(alpha / sigma) as distinct integers allow: the integer
+    whose lambda is nearest each of linspace(lambda(1), lambda(T-1), S) (the lower t on a tie), then made strictly increasing
+    from below, capped at T-1, and made strictly increasing from above.  S = 1: [T-1].  lambda in float64 from ``alphas_cumprod``."""
+    ac = np.asarray(alphas_cumprod).astype(np.float64)
+    T = int(ac.shape[0])
+    if S < 1 or S > T - 1:
+        raise ValueError(f"logsnr spacing: S must be in [1, {T - 1}], got {S}")
+    if S == 1:
+        return np.asarray([T - 1])
+    lam = np.log(np.sqrt(ac) / np.sqrt(1.0 - ac))
+    t = [1 + int(np.argmin(np.abs(lam[1:] - target))) for target in np.linspace(lam[1], lam[T - 1], S)]   # argmin: the first = lower t
+    for k in range(1, S):
+        t[k] = max(t[k], t[k - 1] + 1)
+    t[S - 1] = min(t[S - 1], T - 1)
+    for k in range(S - 2, -1, -1):
+        t[k] = min(t[k], t[k + 1] - 1)
+    return np.asarray(t)
+
+
 class _PLMSBase(object):
     def __init__(self, diffusion, model, schedule="linear", alpha_generator_func=None, set_alpha_scale=None):
         super().__init__()
@@ -66,14 +117,18 @@ class _PLMSBase(object):
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0., verbose=False):
         if ddim_eta != 0:
             raise ValueError('ddim_eta must be 0 for PLMS')
-        self.ddim_timesteps = make_ddim_timesteps(ddim_discretize, ddim_num_steps, self.ddpm_num_timesteps, verbose)
         ac = self.diffusion.alphas_cumprod.detach().to(torch.float32).cpu()
+        self.ddim_timesteps = self._timesteps(ddim_discretize, ddim_num_steps, ac.numpy(), verbose)
         assert ac.shape[0] == self.ddpm_num_timesteps, 'alphas have to be defined for each timestep'
         # float32 values, exactly as the reference's float32 buffers (make_ddim_sampling_parameters, eta = 0)
         self.ddim_alphas = ac[self.ddim_timesteps].numpy()
         self.ddim_alphas_prev = np.asarray([ac[0].item()] + ac[self.ddim_timesteps[:-1]].tolist(), dtype=np.float32)
         self.ddim_sigmas = np.zeros_like(self.ddim_alphas)
         self.ddim_sqrt_one_minus_alphas = torch.sqrt(1.0 - ac[self.ddim_timesteps]).numpy()
+
+    def _timesteps(self, discretize, S, ac, verbose=False):
+        """The S timesteps of a run, ascending (``ac``: the float32 alphas_cumprod); the DPM-Solver++ samplers add a spacing."""
+        return make_ddim_timesteps(discretize, S, self.ddpm_num_timesteps, verbose)
 
     # ---- engine plumbing --------------------------------------------------------------------------------
     @property
@@ -672,32 +727,21 @@ class PLMSSamplerInst(_PLMSBase):
                             list(range(n_img)))
 
 
-class DDIMSampler(_PLMSBase):
-    """ddim.py:7-131.  ``eta`` > 0 (stochastic sampling) and the ``mask`` / ``x0`` inpainting blend included.
-
-    Noise comes from ONE overridable attribute, ``noise_fn(shape) -> fp32 tensor on the engine's device`` (default
-    ``torch.randn``), in the reference's order within a step: the q_sample draw (ldm.py:18), then the step's (ddim.py:128).
-    Deliberate deviation: at ``sigma_t == 0`` no step noise is drawn -- the reference draws one and multiplies it by zero; the
-    values are the same, the consumption of the random stream is not."""
+class _OneForwardSampler(_PLMSBase):
+    """The loop of the samplers whose step is ONE forward and one fused update launch (``DDIMSampler``, ``DPMSolverSampler``):
+    ddim.py:79-105 with the step rule left to ``_step_update``.  Noise comes from ONE overridable attribute,
+    ``noise_fn(shape) -> fp32 tensor on the engine's device`` (default ``torch.randn``)."""
 
     def __init__(self, diffusion, model, schedule="linear", alpha_generator_func=None, set_alpha_scale=None):
         super().__init__(diffusion, model, schedule, alpha_generator_func, set_alpha_scale)
         self.noise_fn = lambda shape: torch.randn(tuple(shape), device=self.engine.device, dtype=torch.float32)
 
-    # ---- schedule (ddim.py:25-54; util.py:55-83) ------------------------------------------------------------
-    def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.):
-        super().make_schedule(ddim_num_steps, ddim_discretize, 0.)             # timesteps, a_t, a_prev, sqrt(1 - a_t): float32
-        self.ddim_sigmas = ddim_sigmas(self.ddim_alphas, self.ddim_alphas_prev, ddim_eta)
+    def _step_update(self, img, e_c, e_u, guidance_scale, i, index, hist):
+        """The update behind step i's forward (``index`` = its place in the schedule arrays): the raw eps halves -> the new latents.
+        ``hist``: a list the rule may keep its history in, empty at the first step."""
+        raise NotImplementedError
 
-    @torch.no_grad()
-    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, eta=0.):
-        """``eta`` is an extension: the reference's ``sample`` always schedules eta 0 (ddim.py:59); its eta is reachable through
-        ``make_schedule(S, ddim_eta=eta)`` + ``ddim_sampling``, which works here too."""
-        self.make_schedule(ddim_num_steps=S, ddim_eta=eta)
-        return self.ddim_sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
-
-    @torch.no_grad()
-    def ddim_sampling(self, shape, input, uc, guidance_scale=1, mask=None, x0=None):
+    def _sampling(self, shape, input, uc, guidance_scale=1, mask=None, x0=None):
         eng = self.engine
         ops = eng.ops
         dev = eng.device
@@ -725,6 +769,7 @@ class DDIMSampler(_PLMSBase):
         total = self.ddim_timesteps.shape[0]
         alphas = self.alpha_generator_func(len(time_range)) if self.alpha_generator_func is not None else None
         self._check_first_conv(alphas)
+        hist: list = []
         for i, step in enumerate(time_range):
             self._apply_alpha(alphas, i)                                      # ddim.py:85-88
             index = total - i - 1
@@ -740,12 +785,40 @@ class DDIMSampler(_PLMSBase):
                 e_c, e_u = e2[:b], e2[b:]
             else:
                 e_c, e_u = eng.forward_cond(img, t, pair), None
-            sigma = float(np.float32(self.ddim_sigmas[index]))
-            noise = self.noise_fn(img.shape) if sigma != 0 else None
-            img = ops.ddim_update(img, e_c, e_u, guidance_scale, float(self.ddim_alphas[index]), float(self.ddim_alphas_prev[index]),
-                                  sigma, float(self.ddim_sqrt_one_minus_alphas[index]), noise, ops.empty(img.shape, torch.float32))
+            img = self._step_update(img, e_c, e_u, guidance_scale, i, index, hist)
             input["x"] = img
         return img
+
+
+class DDIMSampler(_OneForwardSampler):
+    """ddim.py:7-131.  ``eta`` > 0 (stochastic sampling) and the ``mask`` / ``x0`` inpainting blend included.
+
+    Noise comes from ``noise_fn`` in the reference's order within a step: the q_sample draw (ldm.py:18), then the step's (ddim.py:128).
+    Deliberate deviation: at ``sigma_t == 0`` no step noise is drawn -- the reference draws one and multiplies it by zero; the
+    values are the same, the consumption of the random stream is not."""
+
+    # ---- schedule (ddim.py:25-54; util.py:55-83) ------------------------------------------------------------
+    def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.):
+        super().make_schedule(ddim_num_steps, ddim_discretize, 0.)             # timesteps, a_t, a_prev, sqrt(1 - a_t): float32
+        self.ddim_sigmas = ddim_sigmas(self.ddim_alphas, self.ddim_alphas_prev, ddim_eta)
+
+    @torch.no_grad()
+    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, eta=0.):
+        """``eta`` is an extension: the reference's ``sample`` always schedules eta 0 (ddim.py:59); its eta is reachable through
+        ``make_schedule(S, ddim_eta=eta)`` + ``ddim_sampling``, which works here too."""
+        self.make_schedule(ddim_num_steps=S, ddim_eta=eta)
+        return self.ddim_sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
+
+    @torch.no_grad()
+    def ddim_sampling(self, shape, input, uc, guidance_scale=1, mask=None, x0=None):
+        return self._sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
+
+    def _step_update(self, img, e_c, e_u, guidance_scale, i, index, hist):
+        ops = self.engine.ops
+        sigma = float(np.float32(self.ddim_sigmas[index]))
+        noise = self.noise_fn(img.shape) if sigma != 0 else None
+        return ops.ddim_update(img, e_c, e_u, guidance_scale, float(self.ddim_alphas[index]), float(self.ddim_alphas_prev[index]),
+                               sigma, float(self.ddim_sqrt_one_minus_alphas[index]), noise, ops.empty(img.shape, torch.float32))
 
 
 class DDIMSamplerInst(PLMSSamplerInst):
@@ -778,6 +851,10 @@ class DDIMSamplerInst(PLMSSamplerInst):
     @torch.no_grad()
     def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, eta=0.):
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta)
+        return self._sample_call(shape, input, uc, guidance_scale, mask, x0)
+
+    def _sample_call(self, shape, input, uc, guidance_scale, mask, x0):
+        """``sample`` behind ``make_schedule``."""
         self._inpaint = None
         if mask is not None:
             assert x0 is not None
@@ -796,6 +873,10 @@ class DDIMSamplerInst(PLMSSamplerInst):
         4, H, W] and an x0 [1 or K_l, 4, H, W], or None for a layout that is not inpainted (it gets an all-zero mask, which leaves its
         latents bit for bit as they are; the q_sample draw still covers its images)."""
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta)
+        return self._layouts_call(layouts, uc, guidance_scale, masks, x0s)
+
+    def _layouts_call(self, layouts, uc, guidance_scale, masks, x0s):
+        """``sample_layouts`` behind ``make_schedule``: the per-layout masks / x0s stacked one row per image, then the two phases."""
         self._inpaint = None
         if masks is None and x0s is not None and any(x is not None for x in x0s):
             raise ValueError("sample_layouts: x0s without masks; masks and x0s hold one entry per layout, both given or both None")
@@ -882,9 +963,8 @@ class DDIMSamplerInst(PLMSSamplerInst):
 
     def _advance(self, x, hist, i, time_range, total, pair, n, guided, guidance_scale, first=None, rows_img=None):
         """The blend (when inpainting) and p_sample_ddim (ddim.py:107-131): one batched [cond | uncond] forward, its raw halves into
-        the fused update."""
+        the fused update (``_step_update``)."""
         eng = self.engine
-        ops = eng.ops
         run = self._run
         step, index = int(time_range[i]), total - i - 1
         tab = self._table(rows_img)
@@ -900,8 +980,13 @@ class DDIMSamplerInst(PLMSSamplerInst):
                 e_c, e_u = e2[:n], e2[n:]
             else:
                 e_c, e_u = eng.forward_cond(x, t, pair), None
+        return self._step_update(x, e_c, e_u, guidance_scale, i, index, hist, tab)
+
+    def _step_update(self, x, e_c, e_u, guidance_scale, i, index, hist, tab):
+        """The update behind step i's forward: the raw eps halves -> the new rows; ``tab``: ``_table`` of the rows."""
+        ops = self.engine.ops
         sigma = float(np.float32(self.ddim_sigmas[index]))
-        noise = run["step_noise"][i] if sigma != 0 else None
+        noise = self._run["step_noise"][i] if sigma != 0 else None
         args = (guidance_scale, float(self.ddim_alphas[index]), float(self.ddim_alphas_prev[index]), sigma,
                 float(self.ddim_sqrt_one_minus_alphas[index]), noise)
         out = ops.empty(x.shape, torch.float32)
@@ -919,3 +1004,84 @@ class DDIMSamplerInst(PLMSSamplerInst):
     @staticmethod
     def _history_stack(rows):
         return None
+
+
+class _DPMSolverRule(object):
+    """DPM-Solver++(2M), data-prediction form (Lu et al. 2022, "DPM-Solver++", Algorithm 2; the reference has no DPM solver): what
+    ``DPMSolverSampler`` and ``DPMSolverSamplerInst`` share.  A step is one forward and ONE ``idf_dpmpp_update`` launch on the raw
+    [cond | uncond] eps halves; its history is the previous step's x0 prediction.  Steps are deterministic."""
+
+    order = 2
+
+    def _timesteps(self, discretize, S, ac, verbose=False):
+        if discretize == "logsnr":
+            return logsnr_timesteps(S, ac)
+        return super()._timesteps(discretize, S, ac, verbose)
+
+    def _set_order(self, order):
+        if order not in (1, 2):
+            raise ValueError(f"DPM-Solver++: order must be 1 or 2, got {order!r}")
+        self.order = int(order)
+
+    def _dpmpp(self, x, e_c, e_u, guidance_scale, index, hist):
+        """``hist``: [] at the first step of a trajectory, else [the previous step's x0 prediction] (order 2 only: order 1 keeps none,
+        so it never passes an x0_last)."""
+        ops = self.engine.ops
+        last = hist[0] if hist else None
+        a_t = self.ddim_alphas[index]
+        c_x, c_0, c_1 = dpmpp_coeffs(a_t, self.ddim_alphas_prev[index], self.ddim_alphas[index + 1] if last is not None else None)
+        x0_t = ops.empty(x.shape, torch.float32)
+        out = ops.dpmpp_update(x, e_c, e_u, guidance_scale, float(np.sqrt(np.float32(a_t))), float(self.ddim_sqrt_one_minus_alphas[index]),
+                               float(c_x), float(c_0), float(c_1), last, ops.empty(x.shape, torch.float32), x0_t)
+        if self.order == 2:
+            hist[:] = [x0_t]
+        return out
+
+
+class DPMSolverSampler(_DPMSolverRule, _OneForwardSampler):
+    """DPM-Solver++(2M) on ``DDIMSampler``'s loop: the alpha gate, the first-conv check and the optional ``mask`` / ``x0`` inpainting
+    blend in front of each step (its q_sample draw, from ``noise_fn``, is the only noise).  ``order`` 1 is DDIM with eta 0 up to the
+    rounding of the coefficients; ``discretize``: "uniform" (PLMS's and DDIM's timesteps) or "logsnr" (``logsnr_timesteps``)."""
+
+    def make_schedule(self, ddim_num_steps, ddim_discretize="uniform"):
+        super().make_schedule(ddim_num_steps, ddim_discretize, 0.)
+
+    @torch.no_grad()
+    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, order=2, discretize="uniform"):
+        self._set_order(order)
+        self.make_schedule(S, discretize)
+        return self._sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
+
+    def _step_update(self, img, e_c, e_u, guidance_scale, i, index, hist):
+        return self._dpmpp(img, e_c, e_u, guidance_scale, index, hist)
+
+
+class DPMSolverSamplerInst(_DPMSolverRule, DDIMSamplerInst):
+    """The Multi-instance Sampler on DPM-Solver++(2M) steps: ``DDIMSamplerInst`` (units, bank, chunking, hoist, merge, sharding, the
+    inpainting blend through the unit table) with the step's update and the history swapped.  There is no eta: the schedule's sigmas
+    are zero, so the q_sample draw is the only noise.  As with PLMS, phase 2 continues from the history of the image's GLOBAL unit:
+    its first step is second order when there was a phase 1.  The hoisted first evaluation feeds the first-order first step."""
+
+    def make_schedule(self, ddim_num_steps, ddim_discretize="uniform"):
+        super().make_schedule(ddim_num_steps, ddim_discretize, 0.)
+
+    @torch.no_grad()
+    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, order=2, discretize="uniform"):
+        self._set_order(order)
+        self.make_schedule(S, discretize)
+        return self._sample_call(shape, input, uc, guidance_scale, mask, x0)
+
+    @torch.no_grad()
+    def sample_layouts(self, S, layouts, uc=None, guidance_scale=1, order=2, discretize="uniform", masks=None, x0s=None):
+        """``DDIMSamplerInst.sample_layouts`` with ``order`` / ``discretize`` in place of ``eta``."""
+        self._set_order(order)
+        self.make_schedule(S, discretize)
+        return self._layouts_call(layouts, uc, guidance_scale, masks, x0s)
+
+    def _step_update(self, x, e_c, e_u, guidance_scale, i, index, hist, tab):
+        return self._dpmpp(x, e_c, e_u, guidance_scale, index, hist)
+
+    # the history travels as PLMS's eps history does: a list of [rows, ...] tensors, here at most one
+    _new_history = PLMSSamplerInst._new_history
+    _history_row = staticmethod(PLMSSamplerInst._history_row)
+    _history_stack = staticmethod(PLMSSamplerInst._history_stack)

@@ -540,6 +540,17 @@ class HipOps:
                                             self._stream()), "idf_ddim_update")
         return out
 
+    def dpmpp_update(self, x, e_cond, e_uncond, guidance, sqrt_at, sqrt_1m_at, c_x, c_0, c_1, x0_last, out, x0_out):
+        """One DPM-Solver++(2M) step behind the forward: guidance (``e_uncond`` None: unguided), x0_out = (x - sqrt_1m_at e) / sqrt_at,
+        out = c_x x + c_0 x0_out (+ c_1 x0_last; ``x0_last`` None: order 1).  fp32, contiguous, all of ``out``'s size; ``out`` may be
+        ``x``, ``x0_out`` may be ``x0_last``.  -> out."""
+        for t in (x, e_cond, out, x0_out) + tuple(t for t in (e_uncond, x0_last) if t is not None):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == out.numel()
+        _lib.check(self.lib.idf_dpmpp_update(_p(x), _p(e_cond), _p(e_uncond), float(guidance), float(sqrt_at), float(sqrt_1m_at),
+                                             float(c_x), float(c_0), float(c_1), _p(x0_last), _p(out), _p(x0_out), out.numel(),
+                                             self._stream()), "idf_dpmpp_update")
+        return out
+
     def q_sample_blend(self, x0, noise, mask, img, sqrt_ac, sqrt_1m_ac, out):
         """q_sample + the inpainting blend (ldm.py:17-20, ddim.py:94-98): out = (sqrt_ac x0 + sqrt_1m_ac noise) mask + (1 - mask) img.
         x0 / noise / img / out [B,C,H,W] fp32, mask [B,1,H,W] or [B,C,H,W]; ``out`` may be ``img``."""
