@@ -132,7 +132,8 @@ enum { IDF_STAT_GEMM_BIG_LAUNCHES = 0, IDF_STAT_ATTN2_LAUNCHES = 1, IDF_STAT_GEM
                                           once per workgroup, which walks several query blocks); a new enum value within ABI 5, as knob 9 was;
                                           stat id 5 stays unassigned */,
        IDF_STAT_CLIP_PREPROC_LAUNCHES = 12 /* idf_clip_crop_resize launches; a new enum value within ABI 5; id 11 stays unassigned -- it is
-                                              the id the C-ABI tests probe as the first unknown counter, idf_get_stat(11) == -1 */ };
+                                              the id the C-ABI tests probe as the first unknown counter, idf_get_stat(11) == -1 */,
+       IDF_STAT_SKIP_FOLD_LAUNCHES = 13 /* idf_conv3x3_skip calls that ran (also counted in stat 0); a new enum value within ABI 5 */ };
 long long idf_get_stat(int stat);
 
 /* ---- GEMM: out[M,N] = epi( A[M,K] . W[N,K]^T ) ----------------------------------------------------------
@@ -246,6 +247,30 @@ int idf_conv3x3_down(const idf_conv3x3_args* a, void* stream);
  * grid that passes its occupancy bar; any other shape returns IDF_E_UNSUPPORTED BEFORE any launch and the caller runs
  * idf_conv3x3(upsample = 1) with the 3x3 image.  Added within ABI 5 like idf_conv3x3_down: a new symbol only. */
 int idf_conv_up2x_folded(const idf_conv3x3_args* a, void* stream);
+/* ResBlock tail (openaimodel.py:237-257 with a 1x1 `skip_connection`): out = conv3x3(g) + Wskip . x + (b_conv + b_skip) as ONE
+ * contraction over K = 9 C2 + Cx -- the shortcut runs as Cx / 64 extra K-tiles of the conv that read x at the output pixel itself,
+ * instead of a GEMM that writes its 16-bit result to memory and a residual epilogue that reads it back.
+ *   g [B, H, W, C2] (row stride ldg) is the conv input, x [B, H, W, Cx] (row stride ldx) the shortcut input; pad 1, stride 1.
+ *   W is ONE image [Cout][9 C2 + Cx]: the conv taps (ky*3+kx)*C2 + ci first, then the Cx shortcut columns; bias (f32 [Cout], or NULL)
+ *   is the SUM of the two layers' biases (add them in fp32 at pack time).  C2 % 64 == Cx % 64 == 0.
+ *   out [B, H, W, Cout] 16-bit NHWC (row stride ldo); ws / ws_bytes: the optional fp32 split-K workspace of idf_conv3x3;
+ *   gn_partial: idf_conv3x3's contract (statistics of the full output, shortcut included).
+ * Runs on the persistent 256 x 320 kernel only (counted in IDF_STAT_GEMM_BIG_LAUNCHES and IDF_STAT_SKIP_FOLD_LAUNCHES): needs
+ * Cout % 320 == 0 and a launch the dispatch rules of idf_conv3x3 would hand to that kernel; anything else returns
+ * IDF_E_UNSUPPORTED BEFORE any launch and the caller runs idf_gemm + idf_conv3x3(res =) as before.  A null g / x / W / out, a
+ * non-positive size, a C2 or Cx that is not a multiple of 64: IDF_E_ARG; a row stride % 8 or a pointer that is not 16-B aligned
+ * (gn_partial: 8-B): IDF_E_ALIGN; all before any launch.  The shortcut does not pass through a 16-bit rounding here, so results differ
+ * from the two-launch form by that rounding.  Added within ABI 5 like idf_conv_up2x_folded: a new symbol and a new struct only. */
+typedef struct {
+  const void* g; const void* x; const void* W; void* out;
+  const float* bias;
+  int B, H, Wd, C2, Cx, Cout;
+  int ldg, ldx, ldo;
+  int dtype;
+  void* ws; long long ws_bytes;
+  float* gn_partial;
+} idf_conv3x3_skip_args;
+int idf_conv3x3_skip(const idf_conv3x3_skip_args* a, void* stream);
 
 /* first conv 4->C directly from the fp32 NCHW latent (openaimodel.py:371, :469-480): out NHWC 16-bit */
 int idf_conv_in(const float* x_nchw, const float* w /*[C][Cin][3][3]*/, const float* bias, void* out,

@@ -17,6 +17,7 @@ IDF_STAT_QKV_ROW_LAUNCHES, IDF_STAT_GEGLU_ROW_LAUNCHES = 6, 7
 IDF_STAT_PROJ_ROW_LAUNCHES, IDF_STAT_PROJ_ROW_MIN_M = 8, 9
 IDF_STAT_ATTN_RES_LAUNCHES = 10  # launches served by the resident-key form of the 32-query attention kernel
 IDF_STAT_CLIP_PREPROC_LAUNCHES = 12  # idf_clip_crop_resize launches (11 is unassigned: the tests' first unknown id)
+IDF_STAT_SKIP_FOLD_LAUNCHES = 13     # idf_conv3x3_skip calls that ran (also counted in stat 0)
 IDF_CLIP_SRC_U8, IDF_CLIP_SRC_F32 = 0, 1  # idf_clip_crop_resize source kinds
 CLIP_RESIZE_KMAX = 32                # IDF_CLIP_RESIZE_KMAX
 IDF_TUNE_PROJ_ROW = 9            # (8 is unassigned: idf_set_tuning(8, ..) is IDF_E_ARG)
@@ -53,6 +54,12 @@ class ConvArgs(C.Structure):
                 ("n_valid", ci), ("epi", ci), ("dtype", ci), ("ws", vp), ("ws_bytes", ll), ("gn_partial", vp)]
 
 
+class ConvSkipArgs(C.Structure):
+    _fields_ = [("g", vp), ("x", vp), ("W", vp), ("out", vp), ("bias", vp),
+                ("B", ci), ("H", ci), ("Wd", ci), ("C2", ci), ("Cx", ci), ("Cout", ci),
+                ("ldg", ci), ("ldx", ci), ("ldo", ci), ("dtype", ci), ("ws", vp), ("ws_bytes", ll), ("gn_partial", vp)]
+
+
 class AttnArgs(C.Structure):
     _fields_ = [("q", vp), ("ldq", ci), ("strideQ", ll), ("nq", ci),
                 ("k0", vp), ("ldk0", ci), ("strideK0", ll), ("vt0", vp), ("ldv0", ci), ("strideV0", ll), ("n0", ci),
@@ -77,6 +84,7 @@ SYMBOLS = {
     "idf_conv3x3": (ci, [C.POINTER(ConvArgs), vp]),
     "idf_conv3x3_down": (ci, [C.POINTER(ConvArgs), vp]),
     "idf_conv_up2x_folded": (ci, [C.POINTER(ConvArgs), vp]),
+    "idf_conv3x3_skip": (ci, [C.POINTER(ConvSkipArgs), vp]),
     "idf_mlp_geglu": (ci, [C.POINTER(MlpArgs), vp]),
     "idf_conv_in": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
     "idf_attention": (ci, [C.POINTER(AttnArgs), vp]),

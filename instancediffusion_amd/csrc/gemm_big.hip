@@ -97,12 +97,14 @@ __device__ __forceinline__ void swap16(const f32x16& c, float* v) {
   }
 }
 template <int DT, int BM, int BN, int TN, bool SPLIT, bool LNS = false, bool STATS = false, bool GLU = false, bool GST = false,
-          bool QG = true /* IDF_EPI_QUICKGELU compiled in: the dense GEMMs; no conv carries the flag */>
+          bool QG = true /* IDF_EPI_QUICKGELU compiled in: the dense GEMMs; no conv carries the flag */,
+          int EPI_MASK = -1 /* the flags this instantiation's launches can carry: SKIPK's are bias-only, and with every other arm
+                               compiled out its tile loop holds no spilled register */>
 __device__ __forceinline__ void big_epilogue(const CoreParams& p, f32x16 (&acc)[TN][TM], int seq, int slice, int tiles_n, int wm,
                                              int wn, int l31_in, int hi_in, float gate, char* stg_in, const float* lnm = nullptr,
                                              const float* lnr = nullptr) {
   constexpr int WN = BN / 2;
-  const int epi = p.epi;
+  const int epi = p.epi & EPI_MASK;
   // opaque copies: everything the epilogue derives from the lane id (row / column offsets, slot addresses) is then computed
   // HERE, per tile, instead of being hoisted out of the tile loop and kept alive -- or spilled -- across the K loop
   int l31 = l31_in, hi = hi_in;
@@ -545,7 +547,7 @@ __device__ unsigned long long idf_big_trace_buf[4][8];
 // Geometry: BM x BN output tile, (BM/64) x 2 waves (wave tile 64 x BN/2), K-tile BKT, NSTG-stage LDS ring.
 //   <256, {320,256}, 64, 2>: ONE 8-wave workgroup per CU (2 x 72 KB stages); <256, 128, 64, 3>: 3 x 48 KB stages.
 template <int DT, int BM, int BN, int BKT, int NSTG, bool CONV, bool SPLIT, bool LNS = false, bool VT = false, bool STATS = false,
-          bool GLU = false, bool GST = false, bool FOLD = false>
+          bool GLU = false, bool GST = false, bool FOLD = false, bool SKIPK = false>
 __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CoreParams p, const int tiles_total) {
   constexpr int WN = BN / 2, TN = WN / 32;
   constexpr int NW = NWAVES;                               // waves per workgroup: (BM / WM) x 2
@@ -598,6 +600,9 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
   auto swz = [](int row) { return CPR == 8 ? ((row >> 1) & 7) : ((row >> 2) & 3); };   // conflict-free ds_read_b128 (see header)
   unsigned woff[W_INST], aoff[A_INST];
   int ayx[A_INST];                                        // conv: (yo*stride-1) << 16 | (xo*stride-1) & 0xffff
+  // SKIPK (ResBlock shortcut as K-tiles behind the nine taps): first row of the loader's output tile (wave-uniform); the tap-9
+  // pieces derive their row's offset into A2 from it instead of keeping A_INST more offsets alive across the K loop
+  [[maybe_unused]] int l_m0 = 0;
   int l_seq, l_kt = 0, l_k0 = 0, l_nk = 0, tap = 0, ci0 = 0;
 
   auto setup_loader = [&](int item) {
@@ -610,6 +615,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
     const int m_tile = tile / tiles_n;
     const int n0 = (tile - m_tile * tiles_n) * BN, m0 = m_tile * BM;
     l_k0 = slice * nk;
+    if constexpr (SKIPK) l_m0 = m0;
 #pragma unroll
     for (int j = 0; j < W_INST; ++j) {
       const int row = RPI * (wave + NW * j) + dr;
@@ -638,7 +644,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
           continue;
         }
         const int y0 = yo * p.stride - p.pad_lo, x0 = xo * p.stride - p.pad_lo;
-        if (p.up == 0) {
+        if (SKIPK || p.up == 0) {
           // no upsampling (all but three convs of a forward): the tap only ADDS a wave-uniform (ky * Win + kx) * lda to the
           // element offset of the row's window origin, and whether a tap falls into the zero padding is one of 9 bits worked
           // out here, once per output tile -- 8 VALU instructions per piece in the K loop instead of 25-30
@@ -659,7 +665,8 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
         aoff[j] = (unsigned)m * (unsigned)p.lda + sw;
       }
     }
-    if (CONV) conv_tap_at(p, l_k0 * BKT, tap, ci0);
+    if constexpr (SKIPK) conv_tap_at_skip(p, l_k0 * BKT, tap, ci0);
+    else if (CONV) conv_tap_at(p, l_k0 * BKT, tap, ci0);
   };
 
   // LDS-DMA pieces of the K-tile the loader stands on: piece i < W_INST = weight rows, else activation rows.  Inline
@@ -679,6 +686,22 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
         const bool ok = (ayx[j] >> tap) & 1;
         const unsigned short* src = ok ? p.A + (aoff[j] + tapoff) : idf_zero_page + dc * 8;
         dma16_v(src, dst);
+      } else if constexpr (SKIPK) {
+        // taps 0..8 as in the plain conv (no upsampling here); "tap 9" = the shortcut's input at the row's own pixel: always
+        // inside the image -- no mask bit, no zero page.  The branch is wave-uniform.
+        if (tap == 9) {
+          // stride 1: output row m is input pixel m; rows beyond M are clamped duplicates as in setup_loader.  32-bit ELEMENT
+          // offset added to the 64-bit base (the launcher bounds M * lda2 below 2^31)
+          const int row = RPI * (wave + NW * j) + dr;
+          const unsigned off2 = (unsigned)min(l_m0 + row, p.M - 1) * (unsigned)p.lda2 + (unsigned)((dc ^ swz(row)) * 8 + ci0);
+          dma16_v(p.A2 + off2, dst);
+        } else {
+          const int ky = tap / 3, kx = tap - ky * 3;
+          const unsigned tapoff = (unsigned)((ky * p.Win + kx) * p.lda + ci0);          // wave-uniform
+          const bool ok = (ayx[j] >> tap) & 1;
+          const unsigned short* src = ok ? p.A + (aoff[j] + tapoff) : idf_zero_page + dc * 8;
+          dma16_v(src, dst);
+        }
       } else if (CONV && p.up == 0) {
         const int ky = tap / 3, kx = tap - ky * 3;
         const unsigned tapoff = (unsigned)((ky * p.Win + kx) * p.lda + ci0);          // wave-uniform
@@ -699,7 +722,8 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
     }
   };
   auto advance_loader = [&]() {
-    if (CONV) conv_tap_step(p, BKT, tap, ci0);
+    if constexpr (SKIPK) conv_tap_step_skip(p, BKT, tap, ci0);
+    else if (CONV) conv_tap_step(p, BKT, tap, ci0);
     if (++l_kt == l_nk) {
       l_kt = 0;
       l_seq += seq_step;
@@ -903,7 +927,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gemm_kernel_big(const CorePara
     } else if constexpr (FOLD) {
       big_epilogue_fold<DT, BM, BN, TN>(p, acc, tile, ph, tiles_n, wm, wn, l31, hi);
     } else {
-      big_epilogue<DT, BM, BN, TN, SPL, LNS, STATS, GLU, GST, !CONV>(p, acc, tile, slice, tiles_n, wm, wn, l31, hi, gate, stg, lnm, lnr);
+      big_epilogue<DT, BM, BN, TN, SPL, LNS, STATS, GLU, GST, !CONV, SKIPK ? IDF_EPI_BIAS : -1>(p, acc, tile, slice, tiles_n, wm, wn, l31, hi, gate, stg, lnm, lnr);
     }
     TR(4)
     // store instructions this wave just issued, at least (see the first K-tile's wait above)
@@ -943,20 +967,21 @@ int num_cu() {
 }
 
 // Which instantiation of gemm_kernel_big a launch runs: the kernel's bool template arguments as named bits.
-enum : unsigned { KB_CONV = 1, KB_SPLIT = 2, KB_LNS = 4, KB_VT = 8, KB_STATS = 16, KB_GLU = 32, KB_GST = 64, KB_FOLD = 128 };
+enum : unsigned { KB_CONV = 1, KB_SPLIT = 2, KB_LNS = 4, KB_VT = 8, KB_STATS = 16, KB_GLU = 32, KB_GST = 64, KB_FOLD = 128, KB_SKIP = 256 };
 
 template <int DT, int BN, int NSTG, unsigned FLAGS = 0>
 int launch_big_cfg(const CoreParams& p, hipStream_t s, int splitk = 1) {
   constexpr int BM = 256, BKT = 64;
   constexpr bool CONV = FLAGS & KB_CONV, SPLIT = FLAGS & KB_SPLIT, LNS = FLAGS & KB_LNS, VT = FLAGS & KB_VT, STATS = FLAGS & KB_STATS,
-                 GLU = FLAGS & KB_GLU, GST = FLAGS & KB_GST, FOLD = FLAGS & KB_FOLD;
-  if constexpr (!(FLAGS & ~KB_CONV) && NSTG == 2) {         // plain GEMM / conv asked to split: its SPLIT twin
-    if (splitk > 1) return launch_big_cfg<DT, BN, NSTG, (FLAGS & KB_CONV) | KB_SPLIT>(p, s, splitk);
+                 GLU = FLAGS & KB_GLU, GST = FLAGS & KB_GST, FOLD = FLAGS & KB_FOLD, SKIPK = FLAGS & KB_SKIP;
+  static_assert(!SKIPK || (CONV && !FOLD), "the shortcut K-tiles extend the plain 3x3 conv only");
+  if constexpr (!(FLAGS & ~(KB_CONV | KB_SKIP)) && NSTG == 2) {   // plain GEMM / conv asked to split: its SPLIT twin
+    if (splitk > 1) return launch_big_cfg<DT, BN, NSTG, (FLAGS & (KB_CONV | KB_SKIP)) | KB_SPLIT>(p, s, splitk);
   }
   if constexpr (!(FLAGS & (KB_SPLIT | KB_LNS | KB_CONV | KB_STATS | KB_GST)) && NSTG == 2) {   // self-normalising LN_ROW: the LNS twin
     if ((p.epi & IDF_EPI_LN_ROW) && !p.ln_stats) return launch_big_cfg<DT, BN, NSTG, (FLAGS & (KB_VT | KB_GLU)) | KB_LNS>(p, s, 1);
   }
-  void (*kern)(const CoreParams, const int) = gemm_kernel_big<DT, BM, BN, BKT, NSTG, CONV, SPLIT, LNS, VT, STATS, GLU, GST, FOLD>;
+  void (*kern)(const CoreParams, const int) = gemm_kernel_big<DT, BM, BN, BKT, NSTG, CONV, SPLIT, LNS, VT, STATS, GLU, GST, FOLD, SKIPK>;
   constexpr int smem = NSTG * (BM + BN) * BKT * 2 + NWAVES * 2048;      // ring + one 2-KB slot per wave (see `stg` in the kernel): 160 KB at BN = 320
   static std::atomic<unsigned long long> attr_done{0};
   if (const int e = idf_lds_optin(reinterpret_cast<const void*>(kern), smem, attr_done)) return e;
@@ -1029,6 +1054,12 @@ int idf_launch_big(const CoreParams& p, int dtype, bool conv, bool force, hipStr
   const bool vt = p.vt_out != nullptr;
   if (vt && (conv || geglu || (p.N % 320) || (p.vt_col0 % 320) || p.vt_col0 <= 0 || p.vt_col0 >= p.N || (p.M % 16) || (p.ld_vt % 8) ||
              !aligned16(p.vt_out) || (p.epi & ~(IDF_EPI_BIAS | IDF_EPI_LN_ROW)))) return IDF_BIG_UNSUPPORTED;
+  // ResBlock shortcut as K-tiles behind the nine taps (idf_conv3x3_skip): the plain pad-1 stride-1 conv on 320-wide tiles, whole
+  // K-tiles per tap and for the shortcut, bias the only epilogue term (the caller summed the two biases)
+  const bool skip = p.A2 != nullptr;
+  if (skip && (!conv || p.stride != 1 || p.up != 0 || p.pad_lo != 1 || p.Cin <= 0 || (p.Cin % BK) || p.Cx <= 0 || (p.Cx % BK) ||
+               p.K != 9 * p.Cin + p.Cx || (p.N % 320) || (p.lda2 % 8) || !aligned16(p.A2) || (p.epi & ~IDF_EPI_BIAS) ||
+               p.Ho != p.Hin || p.Wo != p.Win)) return IDF_BIG_UNSUPPORTED;
   int bn = 0;
   if (geglu && (p.epi & IDF_EPI_GEGLU_P32)) bn = (p.N % 320 == 0) ? 320 : ((p.N % 256 == 0) ? 256 : 0);
   else if (geglu) bn = (p.N % 256 == 0) ? 256 : 0;
@@ -1088,6 +1119,7 @@ int idf_launch_big(const CoreParams& p, int dtype, bool conv, bool force, hipStr
   {                                                       // the loader uses 32-bit element offsets
     const unsigned long long rows = conv ? (unsigned long long)(p.M / (p.Ho * p.Wo)) * p.Hin * p.Win : (unsigned long long)p.M;
     if (rows * (unsigned long long)p.lda >= (1ull << 31) || (unsigned long long)p.N * p.ldw >= (1ull << 31)) return IDF_BIG_UNSUPPORTED;
+    if (skip && (unsigned long long)p.M * (unsigned long long)p.lda2 >= (1ull << 31)) return IDF_BIG_UNSUPPORTED;
   }
   ++idf_stat_big_launches;
   // output-row statistics from the epilogue registers: unsplit dense 16-bit-output GEMMs whose epilogue is the plain one
@@ -1114,6 +1146,8 @@ int idf_launch_big(const CoreParams& p, int dtype, bool conv, bool force, hipStr
     if (conv) return launch_big_cfg<DT, 128, 3, KB_CONV>(p, s);                                                           \
     return launch_big_cfg<DT, 128, 3>(p, s);                                                                              \
   }                                                                                                                       \
+  if (skip) return gst ? launch_big_cfg<DT, 320, 2, KB_CONV | KB_GST | KB_SKIP>(p, s)                                     \
+                       : launch_big_cfg<DT, 320, 2, KB_CONV | KB_SKIP>(pq, s, splitk);                                    \
   if (gst) return launch_big_cfg<DT, 320, 2, KB_CONV | KB_GST>(p, s);                                                     \
   if (conv) return bn == 320 ? launch_big_cfg<DT, 320, 2, KB_CONV>(pq, s, splitk) : launch_big_cfg<DT, 256, 2, KB_CONV>(pq, s, splitk);   \
   return bn == 320 ? launch_big_cfg<DT, 320, 2>(pq, s, splitk) : launch_big_cfg<DT, 256, 2>(pq, s, splitk);

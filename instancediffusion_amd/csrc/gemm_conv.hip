@@ -489,6 +489,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const CoreParams p) 
 // grids of <= 256 tiles, where a launch is a chain of dependent trips to memory -- and is chosen by tile count in launch().
 std::atomic<long long> idf_stat_gn_epi_launches{0};   // idf_conv3x3 calls whose GroupNorm partials came out of the epilogue (idf_get_stat)
 std::atomic<long long> idf_stat_ring_launches{0};     // launches of the latency kernel (idf_get_stat)
+std::atomic<long long> idf_stat_skip_fold_launches{0};   // idf_conv3x3_skip calls that ran (idf_get_stat)
 std::atomic<long long> idf_stat_gegluw_launches{0};   // GEGLU projections served by geglu640w_kernel (idf_get_stat)
 std::atomic<long long> idf_stat_qkvw_launches{0};     // fused q | k | v projections served by qkv320w_kernel (idf_get_stat)
 std::atomic<long long> idf_stat_projw_launches{0};    // N = K = 320 projections served by proj320s_kernel (idf_get_stat)
@@ -735,6 +736,7 @@ extern "C" long long idf_get_stat(int stat) {
   if (stat == IDF_STAT_PROJ_ROW_MIN_M) return gemm_big_mode() > 0 ? idf_projw_min_rows() : 0;
   if (stat == IDF_STAT_ATTN_RES_LAUNCHES) return idf_stat_attn_res_launches.load();
   if (stat == IDF_STAT_CLIP_PREPROC_LAUNCHES) return idf_stat_clip_preproc_launches.load();
+  if (stat == IDF_STAT_SKIP_FOLD_LAUNCHES) return idf_stat_skip_fold_launches.load();
   return -1;
 }
 
@@ -917,4 +919,53 @@ extern "C" int idf_conv_up2x_folded(const idf_conv3x3_args* a, void* stream) {
   p.out = a->out; p.ldo = a->ldo; p.bias = a->bias; p.epi = a->epi; p.rows_per_batch = a->Hin * a->Win;
   const int rc = idf_launch_big_fold(p, a->dtype, big == 2, (hipStream_t)stream);
   return rc == IDF_BIG_UNSUPPORTED ? IDF_E_UNSUPPORTED : rc;
+}
+
+// ResBlock tail: 3x3 conv + 1x1 shortcut as one contraction, the shortcut as K-tiles behind the nine taps of the persistent kernel
+// (gemm_big.hip, SKIPK).  Like the folded upsample no other kernel family carries the form: whatever launch() would not hand to the
+// persistent kernel is IDF_E_UNSUPPORTED before any launch, and the caller runs idf_gemm + idf_conv3x3(res =).
+extern "C" int idf_conv3x3_skip(const idf_conv3x3_skip_args* a, void* stream) {
+  if (!a || !a->g || !a->x || !a->W || !a->out) return IDF_E_ARG;
+  if (a->B <= 0 || a->H <= 0 || a->Wd <= 0 || a->Cout <= 0) return IDF_E_ARG;
+  if (a->C2 <= 0 || (a->C2 % BK) != 0 || a->Cx <= 0 || (a->Cx % BK) != 0) return IDF_E_ARG;
+  if (a->ldg < a->C2 || a->ldx < a->Cx || a->ldo < a->Cout) return IDF_E_ARG;
+  if ((a->ldg % 8) || (a->ldx % 8) || (a->ldo % 8) || !aligned16(a->g) || !aligned16(a->x) || !aligned16(a->W) || !aligned16(a->out) ||
+      (a->bias && !aligned16(a->bias))) return IDF_E_ALIGN;
+  const long long hw = (long long)a->H * a->Wd;
+  if (hw * a->B >= (1ll << 31) || 9ll * a->C2 + a->Cx >= (1ll << 24)) return IDF_E_ARG;
+  if (a->gn_partial) {
+    if ((hw % 64) || (a->Cout % 32) || a->ldo != a->Cout) return IDF_E_ARG;
+    if (((uintptr_t)a->gn_partial) & 7u) return IDF_E_ALIGN;
+  }
+  if (a->dtype != IDF_BF16 && a->dtype != IDF_F16) return IDF_E_UNSUPPORTED;
+  const int big = gemm_big_mode();
+  if (big == 0 || (a->Cout % 320) != 0) return IDF_E_UNSUPPORTED;
+  CoreParams p{};
+  p.Ho = a->H; p.Wo = a->Wd; p.Hin = a->H; p.Win = a->Wd; p.Cin = a->C2; p.stride = 1; p.up = 0; p.pad_lo = 1;
+  p.K = 9 * a->C2 + a->Cx;
+  p.W = (const unsigned short*)a->W; p.ldw = p.K; p.N = a->Cout; p.n_valid = a->Cout;
+  p.A = (const unsigned short*)a->g; p.lda = a->ldg; p.M = a->B * a->H * a->Wd;
+  p.A2 = (const unsigned short*)a->x; p.lda2 = a->ldx; p.Cx = a->Cx;
+  p.out = a->out; p.ldo = a->ldo; p.bias = a->bias; p.epi = a->bias ? IDF_EPI_BIAS : 0; p.rows_per_batch = a->H * a->Wd;
+  p.ws = (float*)a->ws; p.ws_bytes = a->ws ? (size_t)a->ws_bytes : 0;
+  if (a->gn_partial) { p.gn_partial = a->gn_partial; p.gn_hw = (int)hw; }
+  // launch()'s order for a 3x3 conv of these sizes: a grid of at most 128 small (128 x 128) tiles belongs to the latency kernel
+  const long long tiles_small = (long long)((p.N + 127) / 128) * ((p.M + 127) / 128);
+  if (big != 2 && gemm_ring_tiles() > 0 && tiles_small <= 128 && tiles_small <= gemm_ring_tiles()) return IDF_E_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  int splitk = 1, tail_m0 = 0, gst = 0;
+  int rc = idf_launch_big(p, a->dtype, true, big == 2, s, &splitk, nullptr, big == 3 ? &tail_m0 : nullptr, &gst);
+  if (rc == IDF_BIG_UNSUPPORTED) return IDF_E_UNSUPPORTED;
+  if (rc == 0 && splitk > 1) {
+    CoreParams q = p;
+    q.splitk = splitk; q.tail_m0 = tail_m0; q.tail_rows = p.M - tail_m0;
+    if (a->dtype == IDF_BF16) launch_reduce<IDF_BF16>(q, s);
+    else launch_reduce<IDF_F16>(q, s);
+    rc = idf_launch_status();
+  }
+  if (rc == 0) ++idf_stat_skip_fold_launches;
+  if (rc == 0 && gst) ++idf_stat_gn_epi_launches;
+  if (rc == 0 && a->gn_partial && !gst)
+    rc = idf_groupnorm_stats(a->out, a->gn_partial, a->B, (int)hw, a->Cout, (int)hw / 64, a->dtype, stream);
+  return rc;
 }

@@ -46,6 +46,9 @@ struct CoreParams {
   // folded nearest-x2 upsample (gemm_kernel_big<.., FOLD>, idf_conv_up2x_folded): tiles of ONE output parity phase; work item
   // `tile` belongs to phase tile / fold_tiles.  M, Ho, Wo describe the low-resolution image (one phase), W holds four images.
   int fold_tiles;
+  // ResBlock 1x1 shortcut as extra K-tiles of the 3x3 conv (gemm_kernel_big<.., SKIPK>, idf_conv3x3_skip): K = 9 Cin + Cx; the
+  // K-tiles from 9 Cin on read Cx channels of A2 (row stride lda2) at the OUTPUT pixel itself -- a tenth "tap" without padding
+  const unsigned short* A2; int lda2; int Cx;
 };
 
 constexpr int BK = 64;
@@ -101,6 +104,16 @@ __device__ __forceinline__ void conv_tap_at(const CoreParams& p, int k_elem, int
 __device__ __forceinline__ void conv_tap_step(const CoreParams& p, int bk, int& tap, int& ci0) {
   ci0 += bk;
   if (ci0 >= p.Cin) { ci0 = 0; ++tap; }
+}
+// ... and with the tenth source behind the nine taps (CoreParams::A2): K elements from 9 Cin on are "tap 9", whose Cx channels may
+// be more or fewer than Cin, so the tap index saturates there and ci0 runs on to Cx (the K-tile stream of an output tile ends with it)
+__device__ __forceinline__ void conv_tap_at_skip(const CoreParams& p, int k_elem, int& tap, int& ci0) {
+  tap = min(k_elem / p.Cin, 9);
+  ci0 = k_elem - tap * p.Cin;
+}
+__device__ __forceinline__ void conv_tap_step_skip(const CoreParams& p, int bk, int& tap, int& ci0) {
+  ci0 += bk;
+  if (tap < 9 && ci0 >= p.Cin) { ci0 = 0; ++tap; }
 }
 __device__ __forceinline__ bool conv_tap_inside(int yi, int xi, int Hup, int Wup) { return (yi >= 0) & (yi < Hup) & (xi >= 0) & (xi < Wup); }
 

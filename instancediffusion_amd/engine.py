@@ -70,6 +70,10 @@ class EngineKnobs:
     # folded into the weights at pack time (pack_conv_up2x, idf_conv_up2x_folded): 4 Cin multiply-adds per output pixel instead of
     # 9 Cin.  Off: the 3x3 conv with the upsample in its gather (idf_conv3x3 upsample=1).
     up_fold: bool = True
+    # A ResBlock with a 1x1 shortcut (14 of the 22) runs its tail -- conv2 + shortcut + both biases -- as ONE contraction over
+    # K = 9 Cout + Cin (pack_conv3x3_skip, idf_conv3x3_skip): no shortcut GEMM, no 16-bit shortcut tensor written and read back, no
+    # residual phase in conv2's epilogue.  Off, or where the launch is not taken: the GEMM and conv3x3(res=), the same launches as before.
+    skip_fold: bool = True
     # The fused q | k | v launch (see _self_attn), from vt_min_n tokens per sample.  256 (was 1024): at the 16 x 16 level the fused
     # launch (M32768 N3840 K1280, y read once) replaces the q | k GEMM + the batched 62-%-padded V^T GEMM (2.05 ms per 128-row
     # forward at 523 TF): 165.9 -> 164.7 ms per forward on one box, 64 no further gain (profiles/r05_vt_min_n_ab.log)
@@ -80,7 +84,8 @@ class EngineKnobs:
     # field, environment name, default, parser of the raw string (``bool``: strictly "0" or "1")
     _ENV = (("ln_self", "IDF_LN_SELF", "1", int), ("qkv_row", "IDF_QKV_ROW", "1", lambda s: s != "0"), ("geglu_period", "IDF_GEGLU_PERIOD", "32", int),
             ("mlp_fused", "IDF_MLP_FUSED", "1", bool), ("mlp_min_m", "IDF_MLP_MIN_M", "32768", int), ("pair_hoist", "IDF_PAIR_HOIST", "1", bool),
-            ("gn_epi", "IDF_GN_EPI", "1", bool), ("up_fold", "IDF_UP_FOLD", "1", bool), ("vt_global", "IDF_VT_GLOBAL", "1", lambda s: s != "0"),
+            ("gn_epi", "IDF_GN_EPI", "1", bool), ("up_fold", "IDF_UP_FOLD", "1", bool), ("skip_fold", "IDF_SKIP_FOLD", "1", bool),
+            ("vt_global", "IDF_VT_GLOBAL", "1", lambda s: s != "0"),
             ("vt_min_n", "IDF_VT_MIN_N", "256", int), ("debug_paired", "IDF_DEBUG_PAIRED", "0", lambda s: s == "1"))
 
     def __post_init__(self):
@@ -138,6 +143,17 @@ def pack_conv_up2x(w: torch.Tensor) -> torch.Tensor:
                 taps += [cols[0], cols[1]]                     # (ty, tx = 0), (ty, tx = 1): [Cout, Cin] each
             out[py * 2 + px] = torch.stack(taps, dim=1).reshape(co, 4 * ci)
     return out
+
+
+def pack_conv3x3_skip(w_conv: torch.Tensor, b_conv: torch.Tensor, w_skip: torch.Tensor, b_skip: torch.Tensor):
+    """ResBlock tail as one contraction: conv2 fp32 [Cout, C2, 3, 3] and the 1x1 shortcut fp32 [Cout, Cx(, 1, 1)] -> (fp32
+    [Cout, 9*C2 + Cx]: the conv taps (ky*3+kx)*C2 + ci first, then the shortcut columns; fp32 [Cout]: the two biases summed).  Times
+    the row [nine taps of g2 | x] of an output pixel this is conv2(g2) + skip(x), biases included.  The caller rounds the weights to
+    16 bit; the bias stays fp32."""
+    assert w_conv.dim() == 4 and tuple(w_conv.shape[2:]) == (3, 3) and w_conv.dtype == w_skip.dtype
+    w_skip = w_skip.reshape(w_skip.shape[0], w_skip.shape[1])
+    assert w_skip.shape[0] == w_conv.shape[0]
+    return torch.cat([pack_conv3x3(w_conv), w_skip], dim=1).contiguous(), b_conv + b_skip
 
 
 class Cond:
@@ -268,7 +284,11 @@ class UNetEngine(EngineBase):
                  gn2=(self._f32(rb.out_layers[0].weight), self._f32(rb.out_layers[0].bias)),
                  conv2=self._conv(rb.out_layers[3]),
                  skip=None if isinstance(rb.skip_connection, torch.nn.Identity) else self._lin(rb.skip_connection),
-                 emb_off=off[0])
+                 emb_off=off[0], tail=None)
+        if p["skip"] is not None and self.knobs.skip_fold and hasattr(self.ops, "conv3x3_skip"):
+            wt, bt = pack_conv3x3_skip(rb.out_layers[3].weight.detach().float(), rb.out_layers[3].bias.detach().float(),
+                                       rb.skip_connection.weight.detach().float(), rb.skip_connection.bias.detach().float())
+            p["tail"] = _Lin(self._w16(wt), self._f32(bt))
         emb_w.append(rb.emb_layers[1].weight.detach().float())
         emb_b.append(rb.emb_layers[1].bias.detach().float())
         off[0] += rb.out_channels
@@ -569,13 +589,16 @@ class UNetEngine(EngineBase):
         p1 = self._gnp("gnp.h1", B, H * W, Cout)
         h1 = ops.conv3x3(g, p["conv1"].w, self.buf("rb.h1", (B, H, W, Cout)), bias=p["conv1"].b, rowbias=rb, gn_partial=p1)
         g2 = ops.groupnorm(h1, self.buf("gn", h1.shape), p["gn2"][0], p["gn2"][1], 1e-5, True, partial=p1)
+        p2 = self._gnp("gnp.out", B, H * W, Cout) if want_out else None
+        out = self.buf(out_role, (B, H, W, Cout))
+        if p["tail"] is not None and ops.conv3x3_skip(g2, p["tail"].w, x, out, bias=p["tail"].b, gn_partial=p2):
+            return out, p2
         if p["skip"] is not None:
             xs = ops.gemm(x.view(B * H * W, Cin), p["skip"].w, self.buf("rb.skip", (B * H * W, Cout)),
                           bias=p["skip"].b).view(B, H, W, Cout)
         else:
             xs = x
-        p2 = self._gnp("gnp.out", B, H * W, Cout) if want_out else None
-        return ops.conv3x3(g2, p["conv2"].w, self.buf(out_role, (B, H, W, Cout)), bias=p["conv2"].b, res=xs, gn_partial=p2), p2
+        return ops.conv3x3(g2, p["conv2"].w, out, bias=p["conv2"].b, res=xs, gn_partial=p2), p2
 
     def _self_attn(self, a, y, st, handed, B, N, C, kv_extra=None, vis=None):
         """y [B*N, C] residual stream (raw), st [B*N, 2] its LayerNorm statistics (mu, rstd); the LayerNorm itself is folded

@@ -289,6 +289,36 @@ class HipOps:
         _lib.check(rc, "idf_conv_up2x_folded")
         return True
 
+    def conv3x3_skip(self, g2, w_packed, x, out, *, bias=None, gn_partial=None) -> bool:
+        """ResBlock tail in one launch (``idf_conv3x3_skip``): out = conv3x3(g2) + Wskip . x + bias, the 1x1 shortcut as extra K-tiles
+        of the conv.  g2 [B,H,W,C2] and x [B,H,W,Cx] views (channel-contiguous), w_packed [Cout, 9*C2 + Cx] from
+        ``engine.pack_conv3x3_skip`` (conv taps, then the shortcut columns), bias fp32 [Cout] = the two biases summed; out
+        [B,H,W,Cout] 16-bit; ``gn_partial`` as in ``conv3x3``.  Returns False -- nothing launched, ``out`` untouched -- when the
+        persistent kernel does not take the launch; the caller then runs ``gemm`` + ``conv3x3(.., res=)``."""
+        B, H, W_, C2 = g2.shape
+        Cx, Cout = x.shape[-1], w_packed.shape[0]
+        for t in (g2, x, out):
+            assert t.shape[:3] == (B, H, W_) and t.dtype == self.dtype
+            assert t.stride(-1) == 1 and t.stride(1) == W_ * t.stride(2) and t.stride(0) == H * t.stride(1)
+        assert tuple(w_packed.shape) == (Cout, 9 * C2 + Cx) and w_packed.is_contiguous() and w_packed.dtype == self.dtype
+        assert out.shape[-1] == Cout
+        if bias is not None:
+            assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == Cout
+        if gn_partial is not None:
+            assert gn_partial.dtype == torch.float32 and gn_partial.is_contiguous() and out.is_contiguous()
+            assert tuple(gn_partial.shape) == self.gn_partial_shape(B, H * W_, Cout)
+        args = _lib.ConvSkipArgs(
+            g=g2.data_ptr(), x=x.data_ptr(), W=w_packed.data_ptr(), out=out.data_ptr(),
+            bias=None if bias is None else bias.data_ptr(), B=B, H=H, Wd=W_, C2=C2, Cx=Cx, Cout=Cout,
+            ldg=g2.stride(2), ldx=x.stride(2), ldo=out.stride(2), dtype=self.dt,
+            ws=self._splitk_ws().data_ptr(), ws_bytes=self.SPLITK_WS_BYTES,
+            gn_partial=None if gn_partial is None else gn_partial.data_ptr())
+        rc = self.lib.idf_conv3x3_skip(C.byref(args), self._stream())
+        if rc == _lib.E_UNSUPPORTED:
+            return False
+        _lib.check(rc, "idf_conv3x3_skip")
+        return True
+
     def conv_in(self, x_nchw, w, bias, out):
         B, Cin, H, W_ = x_nchw.shape
         assert x_nchw.dtype == torch.float32 and x_nchw.is_contiguous() and out.is_contiguous()

@@ -35,7 +35,8 @@ torch.cuda.synchronize()
 class ShapeTimer(bench.OpTimer):
     def __getattr__(self, name):
         fn = getattr(self.ops, name)
-        if name not in ("gemm", "conv3x3", "attention", "groupnorm", "layernorm", "scaleu_concat", "row_stats", "mlp_geglu", "conv_in", "conv_up2x"):
+        if name not in ("gemm", "conv3x3", "attention", "groupnorm", "layernorm", "scaleu_concat", "row_stats", "mlp_geglu", "conv_in", "conv_up2x",
+                        "conv3x3_skip"):
             return fn
 
         def timed(*a, **k):
@@ -56,6 +57,13 @@ class ShapeTimer(bench.OpTimer):
                 xx, wf, out = a[0], a[1], a[2]
                 key = f"conv {tuple(xx.shape)}->{wf.shape[1]} s1 u1 folded"
                 self.records.append((key, 2.0 * (out.numel() // out.shape[-1]) * wf.shape[1] * wf.shape[2], s, e))
+                return r
+            elif name == "conv3x3_skip":                       # (g2, packed weights [Cout, 9 C2 + Cx], x, out) -> False: not taken
+                if not r:
+                    return r
+                g2, wp, xx, out = a[0], a[1], a[2], a[3]
+                key = f"conv {tuple(g2.shape)}->{wp.shape[0]} s1 u0 +skip{xx.shape[-1]} K{wp.shape[1]}"
+                self.records.append((key, 2.0 * (out.numel() // out.shape[-1]) * wp.shape[0] * wp.shape[1], s, e))
                 return r
             elif name == "attention":
                 q = a[0]
