@@ -403,6 +403,28 @@ int idf_q_sample_blend_units(const float* x0, const float* noise, const float* m
                              float sqrt_ac, float sqrt_1m_ac, float* out, int U, int B, int C, long long HW,
                              int mask_channels /* 1 or C */, void* stream);
 
+/* ---- entering the schedule part of the way: q_sample alone, and a resize of fp32 planes (host/hires.py: img2img starts and the latent
+ * hi-res second pass).  Both were added within ABI 5: new symbols only.  No synchronisation, no allocation; hipGraph-capturable.
+ * idf_q_sample = LatentDiffusion.q_sample (ldm.py:17-20) without a blend:
+ *   out = sqrt_ac * x0 + sqrt_1m_ac * noise        fp32, each operation rounded on its own (nothing contracted): torch's expression bit
+ *   for bit.  16-B accesses where x0, noise and out are 16-B aligned and n % 4 == 0, scalar accesses otherwise (decided per launch).
+ *   out may alias x0.  IDF_E_ARG before any launch: a null pointer, n < 1, a non-finite coefficient.
+ * idf_resize_planes: a separable resize of `planes` fp32 planes, src [planes][Hi][Wi] -> dst [planes][Ho][Wo], driven by DEVICE tables
+ *   that the host builds in float64 (host/hires.resize_tables; torch's F.interpolate(align_corners=False) geometry from exact integer
+ *   arithmetic): xi int32 [Wo] = the first source column of output column ox (may be negative: -2 at the leading outputs of a bicubic
+ *   upscale), xw fp32 [Wo][taps] its weights; yi int32 [Ho]
+ *   and yw fp32 [Ho][taps] likewise for the rows.  taps = 2 (bilinear) or 4 (bicubic).  The launcher cannot read the tables: the kernel
+ *   clamps every idx + k to [0, n-1] where it becomes an address (also torch's border rule), so a wrong table cannot send a load
+ *   outside src.  The expression is fixed, every operation rounded to fp32 on its own:
+ *     row_j = ((s[r_j][c_0] * xw_0 + s[r_j][c_1] * xw_1) + s[r_j][c_2] * xw_2) + s[r_j][c_3] * xw_3
+ *     out   = ((row_0 * yw_0 + row_1 * yw_1) + row_2 * yw_2) + row_3 * yw_3           (taps 2: the first two terms of each)
+ *   Four outputs per thread along x; 16-B stores where Wo % 4 == 0 and dst is 16-B aligned, scalar stores otherwise (decided per
+ *   launch); no LDS, no scratch.  dst must not overlap src.  IDF_E_ARG before any launch: a null pointer, a dimension < 1, taps not
+ *   2 or 4, dst overlapping src; IDF_E_UNSUPPORTED: planes * Ho * Wo >= 2^31. */
+int idf_q_sample(const float* x0, const float* noise, float sqrt_ac, float sqrt_1m_ac, float* out, long long n, void* stream);
+int idf_resize_planes(const float* src, float* dst, const int* xi, const float* xw, const int* yi, const float* yw, int taps /* 2 or 4 */,
+                      int planes, int Hi, int Wi, int Ho, int Wo, void* stream);
+
 /* ---- DPM-Solver++(2M) step (Lu et al. 2022, "DPM-Solver++", Algorithm 2, data-prediction form) behind the UNet forward -------------
  * Added within ABI 5: a new symbol only.  The host computes the three step coefficients in float64 and rounds them to fp32 once
  * (host/samplers.dpmpp_coeffs); per element, every operation rounded to fp32 on its own (nothing contracted, correctly rounded division):

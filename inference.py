@@ -22,6 +22,14 @@ Two neighbours of the path need assets that do not exist offline; both are handl
     fallback, autoencoder / text_encoder / diffusion sub-dicts); without it ``--synthetic_weights`` must be given.
 The SDXL-refiner cascade (``--cascade_strength``, diffusers + downloads) is outside the path.
 
+``--init_image`` with ``--strength F`` and no mask is img2img: the picture is encoded, noised to the timestep of step
+``S - floor(S F)`` and denoised from there (``host/hires.noised_start`` + ``sample_from``).  ``--hires_scale F`` adds a latent hi-res second
+pass behind any first pass: the finished latents are enlarged on the device (``idf_resize_planes``), noised ``--hires_strength`` of
+the way back and the tail of the schedule is denoised at the larger size with the same conditioning (``host/hires.hires_pass``); the
+decoder then writes ``8 round(image_size F)``-pixel PNGs.  Both run the single-trajectory sampler that matches ``--sampler`` on the global
+input; with ``--mis`` > 0 they must enter the schedule behind the Multi-instance phase (strength <= 1 - mis).  Image quality of either
+cannot be judged on ``--synthetic_weights``.
+
 ``--instance_masks json`` makes the JSON's ``mask`` entries (COCO run-length masks) condition generation, as the reference's
 ``eval_local.py`` route does (utils/input.py:161-186); the reference's ``inference.py`` decodes them and throws them away (:249), which
 stays the default (``ignore``).  The masks are decoded and resized on the device (``idf_rle_decode_planes``): only run lengths are uploaded.
@@ -185,6 +193,42 @@ def load_inpaint(args, model, autoencoder, dev):
     return keep.to(dev), autoencoder.encode(image.to(dev))
 
 
+def hires_side(image_size: int, scale: float) -> int:
+    """``--hires_scale``: the second pass's latent side, ``round(image_size * scale)``; it must be a multiple of 8 (three stride-2
+    levels in the UNet, 8 x 8 pixels per latent in the decoder) and larger than ``image_size``."""
+    side = int(round(image_size * scale))
+    if not scale > 1 or side <= image_size:
+        raise SystemExit(f"--hires_scale must be > 1 (and enlarge the {image_size} x {image_size} latents), got {scale}")
+    if side % 8:
+        lo, hi = side // 8 * 8, side // 8 * 8 + 8
+        near = [f"{v / image_size:g} ({v} x {v} latents)" for v in (lo, hi) if v > image_size]
+        raise SystemExit(f"--hires_scale {scale}: the second pass would run {side} x {side} latents, not a multiple of 8; the nearest valid "
+                         f"scales are {' and '.join(near)}")
+    return side
+
+
+def single_sampler(args, diffusion, model, ag):
+    """The single-trajectory sampler that matches ``--sampler`` and the keywords of its ``sample`` / ``sample_from``: what an img2img
+    start and the hi-res second pass run, on the global input."""
+    kw = dict(alpha_generator_func=ag, set_alpha_scale=set_alpha_scale)
+    if args.sampler in ("ddim", "ddim_inst"):
+        return DDIMSampler(diffusion, model, **kw), dict(eta=args.ddim_eta or 0.)
+    if args.sampler in ("dpmpp", "dpmpp_inst"):
+        return DPMSolverSampler(diffusion, model, **kw), dict(order=args.dpm_order, discretize=args.dpm_spacing)
+    return PLMSSampler(diffusion, model, **kw), {}
+
+
+def refuse_start_inside_mis(flag: str, S: int, strength: float, mis: float) -> None:
+    """A run that enters the S-step schedule behind the Multi-instance phase IS the single-trajectory sampler on the global input; one
+    that would enter inside it is refused (not built)."""
+    from instancediffusion_amd.host.hires import steps_for_strength
+    start, _ = steps_for_strength(S, strength)
+    if mis > 0 and start < int(S * mis):
+        raise SystemExit(f"{flag} {strength} with --mis {mis}: the run would enter the {S}-step schedule at step {start}, inside the "
+                         f"Multi-instance phase (steps 0 .. {int(S * mis) - 1}); the limit is strength <= 1 - mis = {1 - mis:g} "
+                         "(or give --mis 0)")
+
+
 def run_layouts(args, paths, model, autoencoder, diffusion, gi, text_encoder, phrase_encoder, dev, dtype):
     """Several ``--input_json``: different layouts, ``--num_images`` images each, sampled in ONE batch (``sample_layouts``; with
     ``--mis 0`` one row-stacked ``PLMSSampler`` / ``DDIMSampler`` call).  Every layout gets the starting noise a single-JSON run
@@ -320,8 +364,43 @@ def main():
                     help="inpainting: PNG of the sampled size whose kept region is held to the original (needs --inpaint_mask)")
     ap.add_argument("--inpaint_mask", type=str, default=None,
                     help="inpainting: grey-scale PNG of the sampled size, >= 128 keeps the original, < 128 is repainted")
+    ap.add_argument("--strength", type=float, default=None,
+                    help="img2img (--init_image without --inpaint_mask): how far the picture is noised back, in (0, 1]; the last "
+                         "floor(steps * strength) steps run.  With --mis > 0: strength <= 1 - mis")
+    ap.add_argument("--hires_scale", type=float, default=None,
+                    help="latent hi-res second pass: enlarge the finished latents by this factor (> 1; round(image_size * F) must be a "
+                         "multiple of 8, e.g. 1.5 -> 96 x 96 latents, 768-pixel images) and denoise the tail of the schedule there")
+    ap.add_argument("--hires_strength", type=float, default=0.5, help="--hires_scale: how far the enlarged latents are noised back, in (0, 1]")
+    ap.add_argument("--hires_steps", type=int, default=None, help="--hires_scale: steps of the second pass's schedule (default: --steps)")
+    ap.add_argument("--hires_mode", choices=["bicubic", "bilinear"], default="bicubic", help="--hires_scale: how the latents are enlarged")
     args = ap.parse_args()
     paths = list(args.input_json)
+    img2img = args.strength is not None
+    hires = args.hires_scale is not None
+    if args.strength is not None and args.inpaint_mask is not None:
+        raise SystemExit("--strength is img2img (--init_image without a mask); with --inpaint_mask the kept region is held at every step "
+                         "and there is no strength")
+    if img2img and args.init_image is None:
+        raise SystemExit("--strength needs --init_image (img2img)")
+    if img2img and not 0.0 < args.strength <= 1.0:
+        raise SystemExit(f"--strength must be in (0, 1], got {args.strength}")
+    if hires and not args.hires_scale > 1:
+        raise SystemExit(f"--hires_scale must be > 1, got {args.hires_scale}")
+    if hires and not 0.0 < args.hires_strength <= 1.0:
+        raise SystemExit(f"--hires_strength must be in (0, 1], got {args.hires_strength}")
+    if hires and args.hires_steps is not None and args.hires_steps < 1:
+        raise SystemExit("--hires_steps must be >= 1")
+    if (img2img or hires) and len(paths) > 1:
+        raise SystemExit("--strength (img2img) and --hires_scale take one --input_json")
+    if (img2img or hires) and args.use_masked_att:
+        raise SystemExit("--strength (img2img) and --hires_scale do not run with --use_masked_att: its mask planes are built for the "
+                         "model's own latent size and a full run")
+    if hires and args.inpaint_mask is not None:
+        raise SystemExit("--hires_scale does not run with inpainting (--inpaint_mask): the mask and x0 exist at the first size only")
+    if img2img:
+        refuse_start_inside_mis("--strength", args.steps, args.strength, args.mis)
+    if hires:
+        refuse_start_inside_mis("--hires_strength", args.hires_steps or args.steps, args.hires_strength, args.mis)
     ddim_inst = args.sampler == "ddim_inst"
     dpm = args.sampler in ("dpmpp", "dpmpp_inst")
     inst_inpaints = args.sampler in ("ddim_inst", "dpmpp_inst")            # the Multi-instance Samplers that take mask / x0
@@ -348,9 +427,9 @@ def main():
         raise SystemExit("--ddim_eta needs --sampler ddim")
     if args.ddim_eta is not None and args.ddim_eta < 0:
         raise SystemExit("--ddim_eta must be >= 0")
-    if (args.init_image is None) != (args.inpaint_mask is None):
+    if (args.init_image is None) != (args.inpaint_mask is None) and not img2img:
         raise SystemExit("inpainting needs both --init_image and --inpaint_mask")
-    if args.init_image is not None and args.mis > 0 and not inst_inpaints:
+    if args.init_image is not None and args.mis > 0 and not inst_inpaints and not img2img:
         raise SystemExit("inpainting (--init_image / --inpaint_mask) runs without the Multi-instance Sampler: give --mis 0")
     if args.keep_best is not None and (args.clip_score is None or args.keep_best < 1):
         raise SystemExit("--keep_best K needs --clip_score and K >= 1")
@@ -405,8 +484,9 @@ def main():
     meta = meta_from_demo_json(data, args.alpha, ckpt=args.ckpt, save_folder_name=save_folder_name, instance_masks=args.instance_masks)
     torch.manual_seed(args.seed)
     starting_noise = torch.randn(args.num_images, 4, model.image_size, model.image_size).to(dev)
+    side2 = hires_side(model.image_size, args.hires_scale) if hires else None
     inpaint = {}
-    loaded = load_inpaint(args, model, autoencoder, dev)
+    loaded = None if img2img else load_inpaint(args, model, autoencoder, dev)
     if loaded is not None:
         inpaint = dict(mask=loaded[0].expand(args.num_images, -1, -1, -1), x0=loaded[1].expand(args.num_images, -1, -1, -1))
 
@@ -423,7 +503,14 @@ def main():
                                args.negative_prompt, use_masked_att=args.use_masked_att, batch=rows)
     ag = partial(alpha_generator, type=meta["alpha_type"])
     shape = (args.num_images, model.in_channels, model.image_size, model.image_size)
-    if args.mis > 0:
+    single, single_kw = single_sampler(args, diffusion, model, ag)         # img2img and the hi-res second pass run this one
+    if img2img:
+        # a start behind the Multi-instance phase is the single-trajectory sampler on the global input (refuse_start_inside_mis)
+        from instancediffusion_amd.host.hires import noised_start
+        x0 = autoencoder.encode(load_init_image(args.init_image, 8 * model.image_size).to(dev)).expand(args.num_images, -1, -1, -1)
+        inp["x"], start = noised_start(single, x0, args.steps, args.strength, starting_noise, **single_kw)   # the seeded noise is the draw
+        samples = single.sample_from(args.steps, shape, inp, start, uc=uc, guidance_scale=args.guidance_scale, **single_kw)
+    elif args.mis > 0:
         extra = {}
         if ddim_inst:
             sampler = DDIMSamplerInst(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale, mis=args.mis)
@@ -450,6 +537,13 @@ def main():
         else:
             sampler = PLMSSampler(diffusion, model, alpha_generator_func=ag, set_alpha_scale=set_alpha_scale)
         samples = sampler.sample(S=args.steps, shape=shape, input=inp, uc=uc, guidance_scale=args.guidance_scale, **inpaint)
+    pass1 = None
+    if hires:
+        from instancediffusion_amd.host.hires import hires_pass
+        pass1 = samples
+        noise2 = torch.randn(args.num_images, model.in_channels, side2, side2).to(dev)     # the next draw behind --seed
+        samples = hires_pass(single, pass1, inp, uc, args.guidance_scale, args.hires_steps or args.steps, args.hires_strength,
+                             (side2, side2), args.hires_mode, noise2, **single_kw)
     images = autoencoder.decode(samples)                                   # inference.py:95
     folder = os.path.join(args.output, save_folder_name)
     report = None
@@ -464,8 +558,10 @@ def main():
         with open(os.path.join(folder, "clip_scores.json"), "w") as f:
             f.write(json.dumps(report, indent=1) + "\n")
     if args.save_latents:
-        torch.save(dict(latents=samples.cpu(), caption=data["caption"], phrases=meta["phrases"]),
-                   os.path.join(folder, "latents.pt"))
+        saved = dict(latents=samples.cpu(), caption=data["caption"], phrases=meta["phrases"])
+        if pass1 is not None:
+            saved["latents_pass1"] = pass1.cpu()
+        torch.save(saved, os.path.join(folder, "latents.pt"))
     print(f"saved {len(names)} images {tuple(images.shape[1:])} to {folder}")
 
 

@@ -106,6 +106,8 @@ SYMBOLS = {
     "idf_q_sample_blend": (ci, [vp, vp, vp, vp, cf, cf, vp, ci, ci, ll, ci, vp]),
     "idf_ddim_update_units": (ci, [vp, vp, vp, cf, cf, cf, cf, cf, vp, vp, vp, vp, ci, ci, ll, vp]),
     "idf_q_sample_blend_units": (ci, [vp, vp, vp, vp, vp, cf, cf, vp, ci, ci, ci, ll, ci, vp]),
+    "idf_q_sample": (ci, [vp, vp, cf, cf, vp, ll, vp]),
+    "idf_resize_planes": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
     "idf_dpmpp_update": (ci, [vp, vp, vp, cf, cf, cf, cf, cf, cf, vp, vp, vp, ll, vp]),
     "idf_mis_merge": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
     "idf_mis_merge_ragged": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),

@@ -10,7 +10,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-gpu-rdc -Wno-unused-resul
 mkdir -p build
 OBJS=""
 PIDS=""
-for f in gemm_conv gemm_big mlp_fused proj320_stream qkv_fused qkv640_fused geglu_fused attention attention4 attention4w attention8 clip clip_preproc mask_input norms scaleu misc convnext; do
+for f in gemm_conv gemm_big mlp_fused proj320_stream qkv_fused qkv640_fused geglu_fused attention attention4 attention4w attention8 clip clip_preproc mask_input hires norms scaleu misc convnext; do
   stale=0
   [ -f build/$f.o ] || stale=1
   for dep in $f.hip common.h gemm_core.h attn_core.h mw_prims.h mw_row.h mlpw_stream.inc qkvw_stream.inc gegluw_stream.inc qkv640w_stream.inc ../../include/idf.h; do

@@ -403,6 +403,31 @@ __global__ void q_sample_blend_kernel(const float* __restrict__ x0, const float*
   }
 }
 
+// ldm.py:17-20 (q_sample) alone: out = sqrt_ac x0 + sqrt_1m_ac noise, blend_elem's first three operations.  out may alias x0 (no
+// __restrict__ on either): a thread reads its own elements before it writes them.
+__device__ __forceinline__ float q_sample_elem(float x0, float nz, float sa, float s1) {
+#pragma clang fp contract(off)
+  const float t1 = sa * x0;
+  const float t2 = s1 * nz;
+  return t1 + t2;                                                                     // ldm.py:19-20
+}
+
+template <int V>
+__global__ void q_sample_kernel(const float* x0, const float* __restrict__ nz, float sa, float s1, float* out, long long n) {
+  static_assert(V == 1 || V == 4, "scalar or 16-B accesses");
+  const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= n) return;                                                                 // V == 4: the launcher guarantees n % 4 == 0
+  if constexpr (V == 4) {
+    const f32x4 xv = *reinterpret_cast<const f32x4*>(x0 + i), nv = *reinterpret_cast<const f32x4*>(nz + i);
+    f32x4 ov;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ov[j] = q_sample_elem(xv[j], nv[j], sa, s1);
+    *reinterpret_cast<f32x4*>(out + i) = ov;
+  } else {
+    out[i] = q_sample_elem(x0[i], nz[i], sa, s1);
+  }
+}
+
 // plms_instance.py:112-135
 __global__ void mis_merge_kernel(const float* __restrict__ lat, const int* __restrict__ boxes, float* __restrict__ out,
                                  int n_inst, int B, int C, int H, int W, int mode) {
@@ -790,6 +815,17 @@ extern "C" int idf_q_sample_blend_units(const float* x0, const float* noise, con
                                         int mask_channels, void* stream) {
   if (!img_of || U < 1 || B < 1) return IDF_E_ARG;              // x0, noise and mask are per image: the table is always needed
   return blend_launch(x0, noise, mask, img, sqrt_ac, sqrt_1m_ac, out, U, C, HW, mask_channels, img_of, B, stream);
+}
+
+extern "C" int idf_q_sample(const float* x0, const float* noise, float sqrt_ac, float sqrt_1m_ac, float* out, long long n, void* stream) {
+  if (!x0 || !noise || !out || n < 1) return IDF_E_ARG;
+  if (!__builtin_isfinite(sqrt_ac) || !__builtin_isfinite(sqrt_1m_ac)) return IDF_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  // 16-B accesses: every pointer aligned and whole vectors (the policy of idf_q_sample_blend)
+  const bool v4 = (n % 4) == 0 && aligned16(x0) && aligned16(noise) && aligned16(out);
+  if (v4) hipLaunchKernelGGL(q_sample_kernel<4>, grid1d(n / 4), dim3(256), 0, s, x0, noise, sqrt_ac, sqrt_1m_ac, out, n);
+  else hipLaunchKernelGGL(q_sample_kernel<1>, grid1d(n), dim3(256), 0, s, x0, noise, sqrt_ac, sqrt_1m_ac, out, n);
+  return idf_launch_status();
 }
 
 extern "C" int idf_mis_merge(const float* lat, const int* boxes, float* out, int n_inst, int B, int C, int H, int W,

@@ -19,7 +19,10 @@ Host mirror of ``ldm/models/diffusion/plms.py`` (PLMSSampler), ``plms_instance.p
     chunking, hoist, merge and sharding and differ in one hook, ``_advance`` ("advance these n rows one step"), and in the history
     that travels from phase 1 to phase 2 (DDIM: none);
   * ``DPMSolverSampler`` / ``DPMSolverSamplerInst``: DPM-Solver++(2M) (the reference has none) on DDIM's loop and on the Multi-instance
-    Sampler: one forward and one ``idf_dpmpp_update`` launch per step, coefficients from ``dpmpp_coeffs``, history = the last x0.
+    Sampler: one forward and one ``idf_dpmpp_update`` launch per step, coefficients from ``dpmpp_coeffs``, history = the last x0;
+  * ``sample_from(S, shape, input, start, ..)`` on the three single-trajectory samplers (``PLMSSampler``, ``DDIMSampler``,
+    ``DPMSolverSampler``; the reference has none): enter the schedule at step ``start`` with a given latent -- img2img starts and the
+    hi-res second pass of ``host/hires.py``.  The ``*Inst`` samplers take no start.
 """
 from __future__ import annotations
 
@@ -185,6 +188,14 @@ class _PLMSBase(object):
             ops.plms_update(x, e_t, old_eps, None, min(len(old_eps), 3) + 1, a_t, a_prev, s1m, new)
         return new, e_t
 
+    def _check_start(self, start):
+        """``start``: the step at which a single-trajectory run enters the S-step schedule made by ``make_schedule`` (``input["x"]`` is
+        the latent ENTERING that step; 0 = a full run).  ValueError outside [0, S-1], before any forward."""
+        total = int(self.ddim_timesteps.shape[0])
+        if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or not 0 <= start < total:
+            raise ValueError(f"start must be an integer in [0, {total - 1}] (the run has {total} steps), got {start!r}")
+        return int(start)
+
     @staticmethod
     def _push(old_eps: list, e_t):
         old_eps.append(e_t)
@@ -196,12 +207,23 @@ class PLMSSampler(_PLMSBase):
     """plms.py:9-167."""
 
     @torch.no_grad()
-    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
+    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, start=0):
+        """``start``: see ``sample_from``."""
         self.make_schedule(ddim_num_steps=S)
-        return self.plms_sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
+        return self.plms_sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0, start=start)
 
     @torch.no_grad()
-    def plms_sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
+    def sample_from(self, S, shape, input, start, uc=None, guidance_scale=1, mask=None, x0=None):
+        """Enter the S-step schedule at step ``start`` (an extension, ``host/hires.py``: img2img starts and the hi-res second pass; the
+        one spelling the three single-trajectory samplers share): ``input["x"]`` is the latent ENTERING step ``start``; steps
+        start .. S-1 run with their ABSOLUTE index, timestep and ``alphas[i]``, so the grounding gate and the first-conv swap fall where
+        they would in a full run.  The history begins empty at ``start`` (here: a predictor step, two forwards); the inpainting blend,
+        with a mask, applies from ``start`` on.  ``start`` 0 is ``sample``, bit for bit; outside [0, S-1]: ValueError before any forward."""
+        return self.sample(S, shape, input, uc, guidance_scale, mask=mask, x0=x0, start=start)
+
+    @torch.no_grad()
+    def plms_sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, start=0):
+        start = self._check_start(start)
         eng = self.engine
         dev = eng.device
         b = shape[0]
@@ -222,7 +244,8 @@ class PLMSSampler(_PLMSBase):
         alphas = self.alpha_generator_func(len(time_range)) if self.alpha_generator_func is not None else None
         self._check_first_conv(alphas)
         old_eps: list = []
-        for i, step in enumerate(time_range):
+        for i in range(start, total):
+            step = time_range[i]
             self._apply_alpha(alphas, i)
             index = total - i - 1
             step_next = int(time_range[min(i + 1, len(time_range) - 1)])
@@ -741,7 +764,9 @@ class _OneForwardSampler(_PLMSBase):
         ``hist``: a list the rule may keep its history in, empty at the first step."""
         raise NotImplementedError
 
-    def _sampling(self, shape, input, uc, guidance_scale=1, mask=None, x0=None):
+    def _sampling(self, shape, input, uc, guidance_scale=1, mask=None, x0=None, start=0):
+        """``start``: see ``PLMSSampler.sample``; the step rule's history begins empty at ``start``."""
+        start = self._check_start(start)
         eng = self.engine
         ops = eng.ops
         dev = eng.device
@@ -770,7 +795,8 @@ class _OneForwardSampler(_PLMSBase):
         alphas = self.alpha_generator_func(len(time_range)) if self.alpha_generator_func is not None else None
         self._check_first_conv(alphas)
         hist: list = []
-        for i, step in enumerate(time_range):
+        for i in range(start, total):
+            step = time_range[i]
             self._apply_alpha(alphas, i)                                      # ddim.py:85-88
             index = total - i - 1
             input["timesteps"] = torch.full((b,), int(step), device=dev, dtype=torch.long)
@@ -808,6 +834,13 @@ class DDIMSampler(_OneForwardSampler):
         ``make_schedule(S, ddim_eta=eta)`` + ``ddim_sampling``, which works here too."""
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta)
         return self.ddim_sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
+
+    @torch.no_grad()
+    def sample_from(self, S, shape, input, start, uc=None, guidance_scale=1, mask=None, x0=None, eta=0.):
+        """``sample`` entered at step ``start`` (see ``PLMSSampler.sample_from``).  ``sample`` and ``ddim_sampling`` keep the reference's
+        argument lists."""
+        self.make_schedule(ddim_num_steps=S, ddim_eta=eta)
+        return self._sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0, start=start)
 
     @torch.no_grad()
     def ddim_sampling(self, shape, input, uc, guidance_scale=1, mask=None, x0=None):
@@ -1051,6 +1084,13 @@ class DPMSolverSampler(_DPMSolverRule, _OneForwardSampler):
         self._set_order(order)
         self.make_schedule(S, discretize)
         return self._sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
+
+    @torch.no_grad()
+    def sample_from(self, S, shape, input, start, uc=None, guidance_scale=1, mask=None, x0=None, order=2, discretize="uniform"):
+        """``sample`` entered at step ``start`` (see ``PLMSSampler.sample_from``): the step at ``start`` is first order."""
+        self._set_order(order)
+        self.make_schedule(S, discretize)
+        return self._sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0, start=start)
 
     def _step_update(self, img, e_c, e_u, guidance_scale, i, index, hist):
         return self._dpmpp(img, e_c, e_u, guidance_scale, index, hist)

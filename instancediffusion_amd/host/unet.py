@@ -214,6 +214,21 @@ class UNetModel(nn.Module):
         if self._engine is not None:
             self._engine.repack_first_conv(new)
 
+    def reinstate_first_conv(self):
+        """Undo ``restore_first_conv_from_SD`` (the reference never does: one sampling run per loaded model).  A SECOND run on this
+        model that re-enters the schedule in front of the alpha == 0 steps (``host/hires.hires_pass``) must see the model's own first
+        conv there, as a full run would; the swap then happens again where its alpha reaches 0.  No-op when nothing is swapped."""
+        if not getattr(self, "_first_conv_swapped", False):
+            return
+        old = self.input_blocks[0][0]
+        new = Conv(self.in_channels, self.model_channels, 3)
+        new.load_state_dict(self.first_conv_state_dict)
+        new.to(old.weight.device)
+        self.input_blocks[0][0] = new
+        self._first_conv_swapped = False
+        if self._engine is not None:
+            self._engine.repack_first_conv(new)
+
     # ---- execution --------------------------------------------------------------------------------
     @property
     def engine(self):

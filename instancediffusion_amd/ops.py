@@ -595,6 +595,32 @@ class HipOps:
                                                B, Cc, HW, int(mask.shape[1]), self._stream()), "idf_q_sample_blend")
         return out
 
+    def q_sample(self, x0, noise, sqrt_ac, sqrt_1m_ac, out):
+        """q_sample alone (ldm.py:17-20): out = sqrt_ac x0 + sqrt_1m_ac noise.  fp32, contiguous, all of ``out``'s size; ``out`` may be
+        ``x0``."""
+        for t in (x0, noise, out):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == out.numel()
+        _lib.check(self.lib.idf_q_sample(_p(x0), _p(noise), float(sqrt_ac), float(sqrt_1m_ac), _p(out), out.numel(), self._stream()),
+                   "idf_q_sample")
+        return out
+
+    def resize_planes(self, src, dst, xi, xw, yi, yw):
+        """``idf_resize_planes``: src [.., Hi, Wi] -> dst [.., Ho, Wo], fp32 contiguous with the same leading dimensions (the planes),
+        no overlap.  Device tables of ``host.hires.resize_tables``: xi int32 [Wo], xw fp32 [Wo, taps], yi int32 [Ho], yw fp32 [Ho, taps],
+        taps 2 or 4 (the kernel clamps every tap index)."""
+        assert src.dim() >= 2 and dst.dim() == src.dim() and tuple(src.shape[:-2]) == tuple(dst.shape[:-2])
+        Hi, Wi, Ho, Wo = int(src.shape[-2]), int(src.shape[-1]), int(dst.shape[-2]), int(dst.shape[-1])
+        planes = src.numel() // max(Hi * Wi, 1)
+        taps = int(xw.shape[-1])
+        for t in (src, dst, xw, yw):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == dst.device
+        for t in (xi, yi):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.device == dst.device
+        assert tuple(xi.shape) == (Wo,) and tuple(xw.shape) == (Wo, taps) and tuple(yi.shape) == (Ho,) and tuple(yw.shape) == (Ho, taps)
+        _lib.check(self.lib.idf_resize_planes(_p(src), _p(dst), _p(xi), _p(xw), _p(yi), _p(yw), taps, planes, Hi, Wi, Ho, Wo,
+                                              self._stream()), "idf_resize_planes")
+        return dst
+
     def ddim_update_units(self, x, e_cond, e_uncond, guidance, a_t, a_prev, sigma_t, sqrt_1m_at, noise, img_of, out, pred_x0=None):
         """``ddim_update`` over U work units whose step noise is one row per IMAGE: x / e_cond / e_uncond / out [U,C,H,W], noise
         [B,C,H,W] or None (needs sigma_t == 0), img_of: int32 [U] on the device (unit u reads noise[img_of[u]]; the kernel clamps the
