@@ -351,8 +351,23 @@ int idf_unifusion_embed(const float* text, const float* loc, const float* tmask,
                         int rows, int text_dim, int D, int dtype, void* stream);
 
 /* ---- samplers: fused CFG + PLMS update (plms.py:121-165) -------------------------------------------------
- * eps buffers hold [cond | uncond] stacked on batch (2n floats-per-half n).  Writes e_t (guided eps) and, if
- * x_out != NULL, x_prev for the Adams-Bashforth order given by n_old (0 -> plain e_t: first-step predictor).   */
+ * Both evaluate torch's fp32 expression with torch's operations in torch's order, every operation rounded to fp32 on its own (nothing
+ * is contracted into an FMA, the divisions are the correctly rounded ones): the result equals the reference's tensor expression bit
+ * for bit, and idf_cfg_combine's e_t is the e of idf_ddim_update on the same eps buffer.  Scalar accesses, one element per thread, any
+ * 4-B aligned pointers; no synchronisation, no allocation; hipGraph-capturable.
+ * idf_cfg_combine (plms.py:126):   e_t = eps_uncond + guidance * (eps_cond - eps_uncond)
+ *   eps_cond / eps_uncond: the two halves of the engine's [cond | uncond] eps buffer (n floats each).  e_t must not overlap an input.
+ *   IDF_E_ARG before any launch: a null pointer, n < 1.
+ * idf_plms_update (plms.py:130-165 with sigma = 0), e' by mode, the sums left to right as written:
+ *   0: e_t (the first step's predictor)   1: (e_t + e_next) / 2   2: (3 e_t - e1) / 2   3: (23 e_t - 16 e1 + 5 e2) / 12
+ *   4: (55 e_t - 59 e1 + 37 e2 - 9 e3) / 24                   e1 / e2 / e3: the eps history, e1 the newest (old_eps[-1])
+ *   pred_x0 = (x - sqrt_1m_at * e') / sqrt(a_t)               (:138)
+ *   x_out   = sqrt(a_prev) * pred_x0 + sqrt(1 - a_prev) * e'  (:141-143)
+ *   The three square roots are taken by the launcher in fp32 (sqrtf; the radicand 1 - a_prev is one fp32 subtraction), as the
+ *   reference's torch.full(...) tensors are; sqrt_1m_at comes from the caller (the reference's ddim_sqrt_one_minus_alphas buffer).
+ *   A pointer the mode does not read may be NULL and is never dereferenced.  x_out must not overlap an input.
+ *   IDF_E_ARG before any launch: a null x / e_t / x_out, n < 1, mode outside 0..4, a null e_next in mode 1, a null e1 in modes 2-4, a
+ *   null e2 in modes 3-4, a null e3 in mode 4, a_t <= 0, a_prev < 0, a_prev > 1, a non-finite a_t / a_prev / sqrt_1m_at.   */
 int idf_cfg_combine(const float* eps_cond, const float* eps_uncond, float guidance, float* e_t,
                     long long n, void* stream);
 int idf_plms_update(const float* x, const float* e_t, const float* e1, const float* e2, const float* e3,
@@ -443,7 +458,16 @@ int idf_dpmpp_update(const float* x, const float* eps_cond, const float* eps_unc
 
 /* ---- Multi-instance Sampler merge (plms_instance.py:112-135) ---------------------------------------------
  * lat: [n_inst+1][B][C][H][W] fp32.  mode 0: mean over the first dim; mode 1: crop-and-paste of instance j's
- * latent box (boxes: int32 [n_inst][4] = int(box*latent_size), reference index order dim2<-x, dim3<-y).      */
+ * latent box (boxes: int32 [n_inst][4] = int(box*latent_size), reference index order dim2<-x, dim3<-y).
+ * Torch's fp32 result bit for bit, each operation rounded on its own:
+ *   mode 0: s = 0.f; for k = 0 .. n_inst, in order: s += lat[k]; out = s / (float)(n_inst + 1)        (:135)
+ *   mode 1: lat[0], then for k = 1 .. n_inst, in order, out[:, :, b0:b2, b1:b3] = lat[k][:, :, b0:b2, b1:b3] with (b0, b1, b2, b3) =
+ *           boxes[k-1]: dim 2 (H) sliced with b0:b2, dim 3 (W) with b1:b3, later instances win (:112-132).  A box may be empty or
+ *           inverted (nothing is pasted) and may reach past H or W (clipped); its coordinates must be >= 0 (a negative index
+ *           counts from the end in the reference's slices; here it would count from row or column 0).
+ * boxes: DEVICE int32, read in mode 1 only.  out must not overlap lat.  Scalar accesses, one element per thread; no allocation, no
+ * synchronisation; hipGraph-capturable.  IDF_E_ARG before any launch: a null lat / out, n_inst < 0, a non-positive B / C / H / W,
+ * mode not 0 or 1, mode 1 with boxes == NULL.      */
 int idf_mis_merge(const float* lat, const int* boxes, float* out, int n_inst, int B, int C, int H, int W,
                   int mode, void* stream);
 /* The same merge over a RAGGED unit list: a batch of images with different instance counts (PLMSSamplerInst.sample_layouts), one
@@ -468,6 +492,8 @@ int idf_mis_merge_ragged(const float* lat, const int* unit_off, const int* boxes
  * normalises them, a second idf_gemm applies V (:194).  n % 4 == 0, lds % 4 == 0, ldp % 4 == 0, scale > 0.
  * idf_pointwise_nchw: 1x1 conv between small channel counts (Cin <= 16) on fp32 NCHW, input pre-scaled by in_scale:
  * AutoencoderKL.decode's `1/scale_factor * z` + post_quant_conv (ldm/models/autoencoder.py:32-35).  bias may be NULL.
+ * One rounding of in_scale * x, then Cin FMAs from the bias.  IDF_E_ARG before any launch: a null x / w / out, Cin > 16, a non-positive
+ * B / Cin / Cout / HW.
  * (The decoder's other layers are idf_conv_in / idf_groupnorm / idf_conv3x3 / idf_gemm calls.)                          */
 int idf_softmax_rows(const float* s, void* p, long long rows, int n, long long lds, long long ldp, float scale,
                      int dtype, void* stream);

@@ -235,30 +235,56 @@ __global__ __launch_bounds__(512, 2) void conv_in_mfma_kernel(const float* __res
   }
 }
 
+// plms.py:126, torch's fp32 expression bit for bit: every operation rounded to fp32 on its own, in the reference's order (no
+// contraction: a product that fed an FMA would skip its rounding), as in ddim_elem below.
 __global__ void cfg_kernel(const float* __restrict__ ec, const float* __restrict__ eu, float g, float* __restrict__ et, long long n) {
+#pragma clang fp contract(off)
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) { const float u = eu[i]; et[i] = u + g * (ec[i] - u); }
+  if (i >= n) return;
+  const float u = eu[i];
+  const float d = ec[i] - u;
+  const float m = g * d;
+  et[i] = u + m;
 }
 
 // plms.py:130-165.  mode 0: e' = e_t; 1: (e_t + e_next)/2; 2: (3 e_t - e1)/2; 3: (23 e_t - 16 e1 + 5 e2)/12;
 // 4: (55 e_t - 59 e1 + 37 e2 - 9 e3)/24.   x_prev = sqrt(a_prev) (x - sqrt(1-a_t) e')/sqrt(a_t) + sqrt(1-a_prev) e'
+// Every operation is rounded to fp32 on its own, left to right as the reference writes the sums, and the divisions are the correctly
+// rounded ones: torch's fp32 expression bit for bit.
 __global__ void plms_kernel(const float* __restrict__ x, const float* __restrict__ et, const float* __restrict__ e1,
                             const float* __restrict__ e2, const float* __restrict__ e3, const float* __restrict__ en,
                             int mode, float sqrt_at, float sqrt_aprev, float sqrt_1m_at, float sqrt_1m_aprev,
                             float* __restrict__ xo, long long n) {
+#pragma clang fp contract(off)
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float e = et[i];
   float ep;
   switch (mode) {
     case 0: ep = e; break;
-    case 1: ep = (e + en[i]) / 2.0f; break;
-    case 2: ep = (3.0f * e - e1[i]) / 2.0f; break;
-    case 3: ep = (23.0f * e - 16.0f * e1[i] + 5.0f * e2[i]) / 12.0f; break;
-    default: ep = (55.0f * e - 59.0f * e1[i] + 37.0f * e2[i] - 9.0f * e3[i]) / 24.0f; break;
+    case 1: { const float s = e + en[i]; ep = s / 2.0f; break; }                                                       // :154
+    case 2: { const float p0 = 3.0f * e; const float s = p0 - e1[i]; ep = s / 2.0f; break; }                           // :157
+    case 3: {                                                                                                         // :160
+      const float p0 = 23.0f * e, p1 = 16.0f * e1[i], p2 = 5.0f * e2[i];
+      const float s1 = p0 - p1;
+      const float s2 = s1 + p2;
+      ep = s2 / 12.0f;
+      break;
+    }
+    default: {                                                                                                        // :163
+      const float p0 = 55.0f * e, p1 = 59.0f * e1[i], p2 = 37.0f * e2[i], p3 = 9.0f * e3[i];
+      const float s1 = p0 - p1;
+      const float s2 = s1 + p2;
+      const float s3 = s2 - p3;
+      ep = s3 / 24.0f;
+      break;
+    }
   }
-  const float pred_x0 = (x[i] - sqrt_1m_at * ep) / sqrt_at;
-  xo[i] = sqrt_aprev * pred_x0 + sqrt_1m_aprev * ep;
+  const float t = sqrt_1m_at * ep;
+  const float pred_x0 = (x[i] - t) / sqrt_at;                                                                         // :138
+  const float a = sqrt_aprev * pred_x0;
+  const float b = sqrt_1m_aprev * ep;                                                                                 // :141
+  xo[i] = a + b;                                                                                                      // :143
 }
 
 // ddim.py:110-131 in one launch: guidance, pred_x0, dir_xt, the noise term.  Every operation is rounded to fp32 on its own, in the
@@ -715,6 +741,9 @@ extern "C" int idf_plms_update(const float* x, const float* e_t, const float* e1
                                float* x_out, long long n, void* stream) {
   if (!x || !e_t || !x_out || n <= 0 || mode < 0 || mode > 4) return IDF_E_ARG;
   if ((mode == 1 && !e_next) || (mode >= 2 && !e1) || (mode >= 3 && !e2) || (mode >= 4 && !e3)) return IDF_E_ARG;
+  // the policy of idf_ddim_update: a root or a quotient that would be inf or NaN is an argument error, not a launch
+  if (!(a_t > 0.0f) || !(a_prev >= 0.0f) || !(a_prev <= 1.0f)) return IDF_E_ARG;
+  if (!__builtin_isfinite(a_t) || !__builtin_isfinite(a_prev) || !__builtin_isfinite(sqrt_1m_at)) return IDF_E_ARG;
   // float32 host arithmetic mirrors the reference's torch.full(...).sqrt() on float32 scalars (plms.py:130-144)
   const float sqrt_at = sqrtf(a_t), sqrt_aprev = sqrtf(a_prev), sqrt_1m_aprev = sqrtf(1.0f - a_prev);
   hipLaunchKernelGGL(plms_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, x, e_t, e1, e2, e3, e_next, mode,

@@ -13,6 +13,8 @@ import math
 import torch
 import torch.nn.functional as F
 
+from tests import plms_cases
+
 
 class EmulOps:
     def __init__(self, dtype=torch.bfloat16, batch_invariant=False):
@@ -308,35 +310,16 @@ class EmulOps:
         return out
 
     def cfg_combine(self, e_cond, e_uncond, guidance, out):
-        out.copy_(e_uncond + guidance * (e_cond - e_uncond))
+        out.copy_(plms_cases.cfg_combine_expr(e_cond, e_uncond, guidance))
         return out
 
     def plms_update(self, x, e_t, old, e_next, mode, a_t, a_prev, sqrt_1m_at, out):
-        if mode == 0:
-            ep = e_t
-        elif mode == 1:
-            ep = (e_t + e_next) / 2
-        elif mode == 2:
-            ep = (3 * e_t - old[-1]) / 2
-        elif mode == 3:
-            ep = (23 * e_t - 16 * old[-1] + 5 * old[-2]) / 12
-        else:
-            ep = (55 * e_t - 59 * old[-1] + 37 * old[-2] - 9 * old[-3]) / 24
-        a_t = torch.tensor(a_t, dtype=torch.float32)
-        a_prev = torch.tensor(a_prev, dtype=torch.float32)
-        pred = (x - sqrt_1m_at * ep) / a_t.sqrt()
-        out.copy_(a_prev.sqrt() * pred + (1.0 - a_prev).sqrt() * ep)
+        assert 0 <= mode <= 4
+        out.copy_(plms_cases.plms_update_expr(x, e_t, old, e_next, mode, a_t, a_prev, sqrt_1m_at))
         return out
 
     def mis_merge(self, lat, boxes_i32, out, mode):
-        if mode == 0:
-            out.copy_(lat.mean(0))
-        else:
-            v = lat[0].clone()
-            for k in range(lat.shape[0] - 1):
-                b = boxes_i32[k].tolist()
-                v[:, :, b[0]:b[2], b[1]:b[3]] = lat[k + 1][:, :, b[0]:b[2], b[1]:b[3]]
-            out.copy_(v)
+        out.copy_(plms_cases.mis_merge_expr(lat, boxes_i32, mode))
         return out
 
     def cast16(self, x_f32, out):

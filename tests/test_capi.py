@@ -54,6 +54,27 @@ def test_argument_validation_without_gpu():
     assert lib.idf_groupnorm_ws_floats(2, 4096) == 2 * 64 * 32 * 2
     assert lib.idf_softmax_rows(None, None, 4, 64, 64, 64, 1.0, 0, None) == -1
     assert lib.idf_pointwise_nchw(None, None, None, None, 1, 4, 4, 16, 1.0, None) == -1
+    assert lib.idf_pointwise_nchw(0x10000, 0x20000, None, 0x30000, 1, 17, 4, 16, 1.0, None) == -1      # Cin <= 16
+    assert lib.idf_pointwise_nchw(0x10000, 0x20000, None, 0x30000, 1, 4, 4, 0, 1.0, None) == -1
+    # the PLMS step kernels and the merge (fake, never dereferenced pointers): every IDF_E_ARG case of include/idf.h
+    def cfg(ec=0x10000, eu=0x20000, out=0x30000, n=256):
+        return lib.idf_cfg_combine(ec, eu, 7.5, out, n, None)
+    assert [cfg(ec=None), cfg(eu=None), cfg(out=None), cfg(n=0), cfg(n=-4)] == [-1] * 5
+
+    def upd(x=0x10000, e_t=0x20000, e1=0x30000, e2=0x40000, e3=0x50000, en=0x60000, mode=4, a_t=0.42, a_prev=0.75, s1m=0.76,
+            out=0x70000, n=256):
+        return lib.idf_plms_update(x, e_t, e1, e2, e3, en, mode, a_t, a_prev, s1m, out, n, None)
+    nan, inf = float("nan"), float("inf")
+    bad = [upd(x=None), upd(e_t=None), upd(out=None), upd(n=0), upd(n=-4), upd(mode=-1), upd(mode=5), upd(mode=1, en=None),
+           upd(mode=2, e1=None), upd(mode=3, e2=None), upd(mode=4, e3=None), upd(a_t=0.0), upd(a_t=-0.1), upd(a_t=nan), upd(a_t=inf),
+           upd(a_prev=-0.1), upd(a_prev=1.5), upd(a_prev=nan), upd(a_prev=inf), upd(s1m=nan), upd(s1m=inf), upd(s1m=-inf)]
+    assert bad == [-1] * len(bad), bad
+
+    def mrg(lat=0x10000, boxes=0x20000, out=0x30000, n_inst=3, B=1, C=4, H=16, W=16, mode=1):
+        return lib.idf_mis_merge(lat, boxes, out, n_inst, B, C, H, W, mode, None)
+    bad = [mrg(lat=None), mrg(out=None), mrg(n_inst=-1), mrg(B=0), mrg(C=0), mrg(H=0), mrg(W=-1), mrg(mode=2), mrg(mode=-1),
+           mrg(boxes=None)]
+    assert bad == [-1] * len(bad), bad
     with pytest.raises(_lib.IdfError):
         _lib.check(-2, "x")
     # self-normalising LN_ROW (ln_stats == NULL): rejected before any launch when batched, without eps, on rows longer
