@@ -124,7 +124,7 @@ def gemm_ref(a, w, *, bias=None, rowbias=None, rows_per_batch=0, ln_row=None, ln
             + GELU_ABS * v.double().abs()
         return want, slack
     if rowbias is not None:
-        idx = torch.arange(acc.shape[-2]) // rows_per_batch
+        idx = torch.arange(acc.shape[-2], device=acc.device) // rows_per_batch
         acc = acc + rowbias.to(cd)[idx]
     slack = K * EPS32 * mag * s
     if act is not None:

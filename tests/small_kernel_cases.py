@@ -47,12 +47,16 @@ def gen(shape, seed, scale=1.0, shift=0.0):
 
 
 # ---- fp64 references ---------------------------------------------------------------------------------------------------------
-def groupnorm_ref(x, gamma, beta, eps, silu):
-    """x [B, HW, C]: 32 groups of C/32 adjacent channels, statistics over (HW, C/32)."""
+def groupnorm_ref(x, gamma, beta, eps, silu, stats=None):
+    """x [B, HW, C]: 32 groups of C/32 adjacent channels, statistics over (HW, C/32).  ``stats`` = (mean, variance) [B, 32] fp64: the
+    statistics the kernel is HANDED (``groupnorm(.., partial=)``) in place of x's own."""
     B, HW, C = x.shape
-    xd = x.double().view(B, HW, 32, C // 32)
-    mu = xd.mean(dim=(1, 3), keepdim=True)
-    var = (xd - mu).pow(2).mean(dim=(1, 3), keepdim=True)
+    xd = x.double().reshape(B, HW, 32, C // 32)
+    if stats is None:
+        mu = xd.mean(dim=(1, 3), keepdim=True)
+        var = (xd - mu).pow(2).mean(dim=(1, 3), keepdim=True)
+    else:
+        mu, var = (s.double().reshape(B, 1, 32, 1) for s in stats)
     y = ((xd - mu) / (var + eps).sqrt()).view(B, HW, C) * gamma.double() + beta.double()
     return y * torch.sigmoid(y) if silu else y
 
